@@ -19,6 +19,11 @@ per GPU, 4 host threads per GPU).
 
 `python bench.py --gpus N` without a torchrun environment re-executes itself under
 torch.distributed.run with N ranks.  One JSON line on stdout (rank 0).
+
+A plain run does only what the headline needs: set-up, the W + K iterations and the rest of the solve
+to eps.  Everything else -- the CPU baselines and the parity window against the reference, the
+configs[2..4] side workloads, the locality variants, the batch workload -- runs with `--full`.
+`--dump-outputs DIR` writes the (x, y, s) the timed solve returned as DIR/{x,y,s}.npy (rank 0).
 """
 import argparse
 import ctypes as C
@@ -163,9 +168,13 @@ def parse():
     ap.add_argument("--aa", type=int, default=0, help="acceleration_lookback (0 = off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-time-to-eps", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and the side workloads (without it: the headline solve only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the solution (x, y, s) of the timed solve as DIR/<name>.npy (a fixed sample above 64 MB in all)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2..4] side measurements (= --secondary none)")
     ap.add_argument("--secondary", choices=["all", "batch", "none"], default="all",
-                    help="side workloads: all = configs[2] SDP, configs[3] batch, configs[4] fp32, locality variant; batch = configs[3] only")
+                    help="side workloads with --full: all = configs[2] SDP, configs[3] batch, configs[4] fp32, locality variant; batch = configs[3] only")
     ap.add_argument("--torchrun", action="store_true",
                     help="re-execute under torch.distributed.run even with --gpus 1 (WORLD_SIZE=1: the collectives still run, over RCCL)")
     ap.add_argument("--fp32-n", type=int, default=4000000, help="configs[4] size (tests shrink it)")
@@ -203,9 +212,30 @@ def parse():
         a = ap.parse_args(json.loads(os.environ["SCS_BENCH_ARGV"]))
     else:
         a = ap.parse_args()
-    if a.no_secondary:
+    if a.no_secondary or not a.full:
         a.secondary = "none"
+    if not a.full:
+        a.no_cpu_baseline = True
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return a
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(outdir, arrays):
+    """arrays (name -> 1-D float32 / float64) -> outdir/<name>.npy.  Above DUMP_MAX_BYTES in all, every array is cut to the same
+    fraction of its entries, taken at positions drawn by a fixed seed (sorted): the same arguments give the same positions."""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= DUMP_MAX_BYTES else (DUMP_MAX_BYTES - 4096 * len(arrays)) / total
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            a = a[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -518,6 +548,34 @@ class HipSolver:
             raise SystemExit("scs_init failed")
         self.lib.scs_amd_set_residuals_every_iter(self.w, 1 if resid_every_iter else 0)
 
+    def fixed_window(self, W, K, profile):
+        """Exactly W + K iterations of a fresh solve of the same problem that cannot stop early (eps_abs = eps_rel = 0; the
+        tolerances enter only the stopping test, so up to the iteration where the solve to eps stopped these are its own
+        iterates); the last K are timed.  For a window that the solve to eps ends inside.  Leaves a fresh workspace on the
+        original settings.  Returns (seconds, iterations timed, stats before, stats after)."""
+        self.lib.scs_finish(self.w)
+        st = self.T.ScsSettings.from_buffer_copy(self.st)
+        st.eps_abs = st.eps_rel = 0.0
+        st.max_iters = W + K
+        self.w = self.lib.scs_init(C.byref(self.prob.data), C.byref(self.prob.k), C.byref(st))
+        if not self.w:
+            raise SystemExit("scs_init failed")
+        import torch
+        self.begin()
+        it = self.steps(W)
+        s0 = self.stats()
+        self.profiling(profile)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        it2 = self.steps(K)
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        s1 = self.stats()
+        self.profiling(False)
+        self.end()
+        self.reinit()
+        return el, it2 - it, s0, s1
+
     def begin(self):
         assert self.lib.scs_amd_solve_begin(self.w, None, 0) == 0
 
@@ -677,7 +735,31 @@ def batch_workload(args, lib_name, rank, world, local_rank, dist, torch, dev, st
     return out
 
 
-def secondary_single_gpu(args, headline_prob=None):
+def psd_large_blocks_cases():
+    """PSD blocks beyond the LDS path (orders > 92: blocked Jacobi iteration, one fused launch per outer step; VERDICT r3 item 2 set
+    targets for exactly these three cases): ms per projection of all blocks, as scripts/bench_psd_sizes.py measures it.  Part of the
+    `secondary` block of --full, measured before any CPU leg of the run starts: these projections wait on host read-backs of their
+    convergence flags, and with CPU legs running beside them they measured 2-3x their standalone time."""
+    from scs_amd import capi, problems
+    try:
+        lib = capi.load("libscsamd.so")
+        rows = []
+        for k, B in ((92, 64), (256, 8), (1024, 1)):
+            pr = problems.random_sdp(200, B, k, 2, 4, seed=1)
+            prob = capi.Problem(pr["A"], pr["b"], pr["c"], pr["cone"])
+            r = capi.solve(lib, prob, verbose=0, acceleration_lookback=0, max_iters=40, eps_abs=1e-12, eps_rel=1e-12, want_stats=True, profiling=True)
+            st = r["stats"]
+            rows.append(dict(order=k, blocks=B, ms_per_projection=st["cone_ms"] / max(st["cone_projs"], 1), projections_timed=st["cone_projs"],
+                             psd_unconverged=st.get("psd_unconverged")))
+        return dict(
+            workload="random SDPs with B PSD blocks of order k (92x64 = the largest order of the LDS kernel; 256x8 and 1024x1 = the blocked "
+                     "iteration of scs_amd/csrc/psd_big.h), 40 ADMM iterations each, cold start, HIP events around the cone kernels",
+            cases=rows, targets_ms="VERDICT r3: 92x64 <= 2, 256x8 <= 2.5, 1024x1 <= 10", evidence="profiles/r6_psd_big.md, profiles/r4_psd_fused_step.md")
+    except Exception as e:
+        return dict(error=str(e))
+
+
+def secondary_single_gpu(args, headline_prob=None, psd_large_blocks=None):
     """Driver-timed side measurements on rank 0 at N=1: BASELINE configs[2] (SDP), configs[4] (fp32)."""
     import torch
     from scs_amd import capi, problems
@@ -711,24 +793,7 @@ def secondary_single_gpu(args, headline_prob=None):
         out["configs2_sdp"] = d
     except Exception as e:
         out["configs2_sdp"] = dict(error=str(e))
-    # ---- PSD blocks beyond the LDS path (orders > 92: blocked Jacobi iteration, one fused launch per outer step; VERDICT r3 item 2 set
-    # targets for exactly these three cases): ms per projection of all blocks, as scripts/bench_psd_sizes.py measures it
-    try:
-        lib = capi.load("libscsamd.so")
-        rows = []
-        for k, B in ((92, 64), (256, 8), (1024, 1)):
-            pr = problems.random_sdp(200, B, k, 2, 4, seed=1)
-            prob = capi.Problem(pr["A"], pr["b"], pr["c"], pr["cone"])
-            r = capi.solve(lib, prob, verbose=0, acceleration_lookback=0, max_iters=40, eps_abs=1e-12, eps_rel=1e-12, want_stats=True, profiling=True)
-            st = r["stats"]
-            rows.append(dict(order=k, blocks=B, ms_per_projection=st["cone_ms"] / max(st["cone_projs"], 1), projections_timed=st["cone_projs"],
-                             psd_unconverged=st.get("psd_unconverged")))
-        out["psd_large_blocks"] = dict(
-            workload="random SDPs with B PSD blocks of order k (92x64 = the largest order of the LDS kernel; 256x8 and 1024x1 = the blocked "
-                     "iteration of scs_amd/csrc/psd_big.h), 40 ADMM iterations each, cold start, HIP events around the cone kernels",
-            cases=rows, targets_ms="VERDICT r3: 92x64 <= 2, 256x8 <= 2.5, 1024x1 <= 10", evidence="profiles/r6_psd_big.md, profiles/r4_psd_fused_step.md")
-    except Exception as e:
-        out["psd_large_blocks"] = dict(error=str(e))
+    out["psd_large_blocks"] = psd_large_blocks
     # ---- the headline problem under the reference's DEFAULT settings: acceleration_lookback = 10 (include/glbopts.h:45),
     # Anderson acceleration device resident (scs_amd/csrc/aa_dev.hip; call sites src/scs.c:1359-1366, :1439-1447)
     try:
@@ -966,6 +1031,10 @@ def main():
         dist.broadcast(desc, src=0)
     n, m, col_nnz, seed, K, W, aa = [int(v) for v in desc.tolist()]
 
+    # ---- --full: the PSD cases of `secondary` before any CPU leg starts (psd_large_blocks_cases)
+    want_secondary = world == 1 and not stub and args.secondary == "all" and args.dtype == "f64"
+    psd_cases = psd_large_blocks_cases() if want_secondary else None
+
     # ---- CPU side leg that needs minutes: the reference to TERMINATION on one configs[3] problem, started first, on its own
     # NUMA node, so that it is done by the time the GPU work is (collected into batch.parity below)
     want_cpu = world == 1 and not args.no_cpu_baseline and args.dtype == "f64" and not stub
@@ -1004,6 +1073,11 @@ def main():
     stats2 = S.stats()
     spmv_kernel_names = S.spmv_kernels()
     res = S.end()
+    # what a caller of the timed solve receives (copied: the re-runs below reuse the buffers)
+    outputs = dict(x=S.x.copy(), y=S.y.copy(), s=S.s.copy()) if (args.dump_outputs and rank == 0 and not stub) else None
+    window_rerun = steps_done < K and not stub
+    if window_rerun:  # the solve stopped inside the window: --steps still sets how many iterations are timed
+        elapsed, steps_done, stats0, stats1 = S.fixed_window(W, K, not args.no_kernel_timing)
 
     red = torch.tensor([elapsed, solve_wall], dtype=torch.float64, device=dev)
     cnt = torch.tensor([steps_done, res["iter"]], dtype=torch.int64, device=dev)
@@ -1122,6 +1196,9 @@ def main():
             "steps": K,
             "warmup": W,
             "ms_per_step": 1e3 * elapsed_max / max(steps_done, 1),
+            "steps_timed": steps_done,
+            **({"window_rerun": "the solve to eps stopped inside the window: the window was timed on a fresh solve of the same problem "
+                                "that cannot stop early (eps_abs = eps_rel = 0)"} if window_rerun else {}),
             "window_it_per_s": total_steps / elapsed_max,
             "us_per_cg_iter": 1e6 * elapsed / cg_its if cg_its else None,
             "higher_is_better": True,
@@ -1184,8 +1261,8 @@ def main():
         if batch_out is not None:
             batch_out.pop("_problem0", None)
             out["batch"] = batch_out
-        if world == 1 and not stub and args.secondary == "all" and args.dtype == "f64":
-            out["secondary"] = secondary_single_gpu(args, headline_prob=getattr(S, "prob", None))
+        if want_secondary:
+            out["secondary"] = secondary_single_gpu(args, headline_prob=getattr(S, "prob", None), psd_large_blocks=psd_cases)
         if want_cpu:
             # the OpenMP legs start while the 1-thread leg is still finishing (one extra core does not disturb them)
             out["cpu_baseline_omp"] = cpu_omp_sweep(args, n, cpu_early, gpu_win)
@@ -1233,6 +1310,8 @@ def main():
                     if ra.get("its_per_s") else dict(error=ra.get("error", str(ra)[:300])))
         else:
             out["cpu_baseline"] = None
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         emit(out, json_fd)
     if dist:
         dist.barrier()

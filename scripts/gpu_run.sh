@@ -4,7 +4,7 @@
 # Steps (each writes under gpurun_out/<tag>/ and prints a short tail):
 #   tests[:<pytest -k expr>]   pytest -m gpu (optionally a subset)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:<extra args>]       the default bench line (compact line -> bench.json, full record -> bench_detail.json)
+#   bench[:<extra args>]       the full bench line, --full (compact line -> bench.json, full record -> bench_detail.json)
 #   profile:<round>            scripts/profile_bench.sh <round>  (rocprofv3 kernel trace + the PMC passes, separate runs)
 #   psd                        scripts/bench_psd_sizes.py + the configs[2] SDP (scripts/bench_sdp.py)
 #   term:<n>:<threads>         scripts/term_parity.py in the BACKGROUND (its CPU leg runs beside the later steps); waited for at the end
@@ -28,7 +28,7 @@ for step in "$@"; do
       tail -6 "$OUT/pytest.log" ;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
     bench)
-      ( time SCS_BENCH_DETAIL="$OUT/bench_detail.json" timeout 900 python bench.py $arg ) > "$OUT/bench.json" 2> "$OUT/bench.err"
+      ( time SCS_BENCH_DETAIL="$OUT/bench_detail.json" timeout 900 python bench.py --full $arg ) > "$OUT/bench.json" 2> "$OUT/bench.err"
       wc -c "$OUT/bench.json"; tail -c 3000 "$OUT/bench.json" ;;
     profile) bash scripts/profile_bench.sh "$arg" 2>&1 | tail -30 ;;
     psd)

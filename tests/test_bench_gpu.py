@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +40,7 @@ def _line_and_detail(out):
 
 def test_two_ranks_share_one_gpu_and_report_one_line():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--n", "20000",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--n", "20000",
                           "--steps", "10", "--warmup", "5", "--no-cpu-baseline", "--batch-n", "4000",
                           "--batch-per-gpu", "2", "--batch-concurrency", "2"],
                          env=env, capture_output=True, text=True, timeout=600)
@@ -56,7 +57,7 @@ def test_two_ranks_share_one_gpu_and_report_one_line():
 def _run_bench(extra, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["MASTER_ADDR"] = "127.0.0.1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
                           "--secondary", "batch", "--batch-n", "20000", "--batch-per-gpu", "2", "--batch-concurrency", "2"] + extra,
                          env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -85,11 +86,11 @@ def test_one_rank_under_torchrun_runs_its_collectives_over_rccl():
 
 
 def test_side_workloads_of_the_default_line_at_reduced_sizes():
-    """The `secondary` block of the default bench line (configs[2] SDP, configs[4] fp32 carried to eps with fp64 host
+    """The `secondary` block of the `--full` bench line (configs[2] SDP, configs[4] fp32 carried to eps with fp64 host
     residuals, the locality variants) and the OpenMP-sweep plumbing, at sizes that take seconds: every field the driver's
     line carries must be there and sane."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "120000", "--fp32-n", "120000", "--steps", "10", "--warmup", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "120000", "--fp32-n", "120000", "--steps", "10", "--warmup", "5",
                           "--batch-n", "8000", "--batch-per-gpu", "2", "--batch-concurrency", "2", "--cpu-omp-sweep", "4", "--cpu-omp-budget", "120",
                           "--cpu-window-iters", "2", "--parity-threads", "4", "--aa-window-threads", "4"], env=env, capture_output=True, text=True,
                          timeout=900)
@@ -143,3 +144,27 @@ def test_side_workloads_of_the_default_line_at_reduced_sizes():
         # (no AA decision falls into the window: the first solve needs acceleration_lookback = 10 samples, one per call, one call
         # every acceleration_interval = 10 iterations -> iteration 100, src/aa.c; the GPU side above runs the whole solve)
         assert ar["accepted_accel_steps"] + ar["rejected_accel_steps"] == 0
+
+
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_solution(tmp_path):
+    """A plain run (no --full) is the headline solve alone: no CPU legs, no side workloads.  --steps sets the number of timed
+    iterations even where the solve to eps stops before warmup + steps (the window is then timed on a fresh solve of the same
+    problem that cannot stop early), and --dump-outputs writes the returned (x, y, s): the same arguments give the same inputs and,
+    the solve being bit-reproducible, the same arrays."""
+    runs = []
+    for tag in ("a", "b"):
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+        env["SCS_BENCH_DETAIL"] = str(tmp_path / f"detail_{tag}.json")
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "20000", "--steps", "3000", "--warmup", "5",
+                              "--dump-outputs", str(tmp_path / tag)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = _line_and_detail(out)
+        assert d["status"] == "solved" and d["iters_to_eps"] < 3005 and d["value"] > 0
+        assert d["steps"] == 3000 and d["steps_timed"] == 3000 and "window_rerun" in d and d["ms_per_step"] > 0
+        assert d["cpu_baseline"] is None and not {"batch", "secondary", "parity_window", "cpu_baseline_omp"} & set(d)
+        arrs = {k: np.load(tmp_path / tag / f"{k}.npy") for k in ("x", "y", "s")}
+        assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in arrs.values())
+        assert arrs["x"].shape == (20000,) and arrs["y"].shape == arrs["s"].shape == (40000,)
+        runs.append(arrs)
+    for k in ("x", "y", "s"):
+        assert np.array_equal(runs[0][k], runs[1][k]), k

@@ -190,7 +190,7 @@ def test_bench_eight_rank_dry_run_over_gloo():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--stub-solver", "--backend", "gloo",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--stub-solver", "--backend", "gloo",
                           "--steps", "3", "--warmup", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -307,3 +307,49 @@ def test_parallel_host_transpose_of_the_b1_boundary_equals_the_serial_one(tmp_pa
     so = str(tmp_path / "libtr.so")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-shared", "-fPIC", "-o", so, os.path.join(here, "native", "host_check_transpose.cpp")])
     assert ctypes.CDLL(so).transpose_check() == 0
+
+
+def test_bench_plain_run_leaves_the_side_workloads_to_full(tmp_path):
+    """Without --full the bench runs the headline solve only (no configs[3] batch, no CPU baseline); --full adds them (stub launch
+    path, no GPU)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["SCS_BENCH_DETAIL"] = str(tmp_path / "detail.json")
+    lines = {}
+    for mode in ([], ["--full"]):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--stub-solver", "--steps", "3", "--warmup", "1",
+                              "--batch-per-gpu", "2"] + mode, capture_output=True, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[bool(mode)] = json.loads(out.stdout.strip().splitlines()[-1])
+    plain, full = lines[False], lines[True]
+    assert plain["cpu_baseline"] is None and "batch" not in plain and plain["steps"] == 3 and plain["ms_per_step"] > 0
+    assert full["batch"]["problems"] == 2 and full["batch"]["all_solved"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_above_64_mb(tmp_path):
+    """--dump-outputs: arrays are written as they are up to 64 MB in all; above, every array is cut to the same fraction of its
+    entries at positions drawn by a fixed seed -- two dumps of the same arrays are identical."""
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    small = dict(x=np.arange(10.0), y=np.arange(5, dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, a in small.items():
+        b = np.load(tmp_path / "small" / f"{k}.npy")
+        assert b.dtype == a.dtype and np.array_equal(a, b)
+    big = dict(x=np.arange(6e6), y=-np.arange(4e6))  # 80 MB
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), big)
+    sizes = 0
+    for k, a in big.items():
+        da, db = (np.load(tmp_path / t / f"{k}.npy") for t in ("a", "b"))
+        assert np.array_equal(da, db) and 0 < da.size < a.size and da.dtype == np.float64
+        assert np.all(np.diff(np.abs(da)) > 0) and np.all(np.isin(da, a))  # a subset, in order
+        sizes += os.path.getsize(tmp_path / "a" / f"{k}.npy")
+    assert sizes <= bench.DUMP_MAX_BYTES

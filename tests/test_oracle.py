@@ -176,3 +176,24 @@ def test_all_cone_restatement_trajectory_equals_reference_with_exact_cg(seed):
     for key in ("pobj", "dobj", "res_pri", "res_dual", "gap", "scale"):
         assert abs(ro["info"][key] - rr["info"][key]) <= 1e-6 * max(abs(rr["info"][key]), 1e-3), key
     assert np.abs(ro["x"] - rr["x"]).max() <= 1e-6 * max(1.0, np.abs(rr["x"]).max())
+
+
+def test_harness_built_elsewhere_finds_the_library_beside_it(tmp_path):
+    """oracle/needed.py: a program linked to a library by its absolute path (as oracle/Makefile's older recipe linked the
+    conformance harnesses) loads again after its directory has moved, through its RUNPATH $ORIGIN."""
+    import shutil
+    import subprocess
+    from oracle import needed
+    built = tmp_path / "built"
+    built.mkdir()
+    (built / "lib.c").write_text("int answer(void) { return 42; }\n")
+    (built / "main.c").write_text("int answer(void);\nint main(void) { return answer() == 42 ? 0 : 1; }\n")
+    subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", str(built / "libanswer.so"), str(built / "lib.c")])
+    subprocess.check_call(["gcc", "-o", str(built / "prog"), str(built / "main.c"), str(built / "libanswer.so"), "-Wl,-rpath,$ORIGIN"])
+    assert subprocess.run([str(built / "prog")]).returncode == 0
+    moved = tmp_path / "moved"
+    shutil.move(str(built), str(moved))
+    assert subprocess.run([str(moved / "prog")], capture_output=True).returncode != 0  # the old path is gone
+    assert needed.fix(str(moved)) == {"prog": [(str(built / "libanswer.so"), "libanswer.so")]}
+    assert subprocess.run([str(moved / "prog")]).returncode == 0
+    assert needed.fix(str(moved)) == {}  # nothing left to rewrite
