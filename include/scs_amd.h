@@ -277,6 +277,9 @@ scs_int scs_amd_linsys_mat_vec_dev(ScsLinSysWork *w, const scs_float *x_dev, scs
 scs_int scs_amd_linsys_mul_a_dev(ScsLinSysWork *w, const scs_float *x_dev, scs_float *y_dev);
 scs_int scs_amd_linsys_mul_at_dev(ScsLinSysWork *w, const scs_float *y_dev, scs_float *x_dev);
 scs_int scs_amd_linsys_sync(ScsLinSysWork *w);
+/* the SpMV kernel these entries (and scs_solve_lin_sys) run for A (which = 0) / A' (which = 1): the strings of
+ * scs_amd_get_spmv_kernel_name.  Returns the length needed. */
+scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap);
 void scs_amd_get_stats(const ScsWork *w, ScsAmdStats *out);
 void scs_amd_set_profiling(ScsWork *w, scs_int on);
 /* scs_solve split in three so a harness can time / inspect an exact range of ADMM

@@ -147,6 +147,8 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # device pointers
         lib.scs_amd_linsys_sync.restype = scs_int
         lib.scs_amd_linsys_sync.argtypes = [C.c_void_p]
+        lib.scs_amd_linsys_spmv_kernel_name.restype = scs_int
+        lib.scs_amd_linsys_spmv_kernel_name.argtypes = [C.c_void_p, scs_int, C.c_char_p, scs_int]
         lib.scs_amd_set_option.restype = scs_int
         lib.scs_amd_set_option.argtypes = [C.c_char_p, C.c_char_p]
         lib.scs_amd_get_option.restype = C.c_char_p

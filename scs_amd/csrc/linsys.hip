@@ -1593,6 +1593,11 @@ scs_int scs_amd_linsys_mul_a_dev(ScsLinSysWork *w, const scs_float *x_dev, scs_f
 scs_int scs_amd_linsys_mul_at_dev(ScsLinSysWork *w, const scs_float *y_dev, scs_float *x_dev) {
   return with_work(w, y_dev, x_dev, [](LinSys &ls, const real *y, real *x) { ls.mul_At(y, x); });
 }
+// the SpMV kernel the workspace runs for A (which = 0) / A' (which = 1): the strings of scs_amd_get_spmv_kernel_name
+scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap) {
+  if (!w) return -1;
+  return (scs_int)spmv_kernel_name(which ? w->ls.At.wave : w->ls.A.wave, buf, cap);
+}
 scs_int scs_amd_linsys_sync(ScsLinSysWork *w) {
   if (!w) return -1;
   if (hipSetDevice(w->device) != hipSuccess) return -1;

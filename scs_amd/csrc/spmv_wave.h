@@ -563,4 +563,22 @@ struct WaveRowsDev {
   }
 };
 
+// the name of the SpMV kernel launch_spmv runs for a matrix whose wave layout is `wv` (null or not built: csr_stream_kernel), as the
+// template instantiation rocprofv3 lists; copies at most cap - 1 characters and a terminating zero, returns the length needed
+// (scs_amd_get_spmv_kernel_name, scs_amd_linsys_spmv_kernel_name)
+inline int spmv_kernel_name(const WaveRowsDev *wv, char *buf, long long cap) {
+  char tmp[96];
+  if (wv && wv->built && wv->wide) snprintf(tmp, sizeof tmp, "csr_wave_wide_kernel<EPI>");
+  else if (wv && wv->built && wv->lockstep) snprintf(tmp, sizeof tmp, "csr_wave_lockstep_kernel<EPI,%d,%d>", wv->ls_wpb, wv->ls_bmode);
+  else if (wv && wv->built) snprintf(tmp, sizeof tmp, "csr_wave_kernel<EPI,%d>", wv->pipelined);
+  else snprintf(tmp, sizeof tmp, "csr_stream_kernel<EPI>");
+  const size_t len = strlen(tmp);
+  if (buf && cap > 0) {
+    const size_t c = std::min(len, (size_t)cap - 1);
+    memcpy(buf, tmp, c);
+    buf[c] = 0;
+  }
+  return (int)len;
+}
+
 } // namespace scsamd
