@@ -277,6 +277,40 @@ scs_int scs_amd_linsys_mat_vec_dev(ScsLinSysWork *w, const scs_float *x_dev, scs
 scs_int scs_amd_linsys_mul_a_dev(ScsLinSysWork *w, const scs_float *x_dev, scs_float *y_dev);
 scs_int scs_amd_linsys_mul_at_dev(ScsLinSysWork *w, const scs_float *y_dev, scs_float *x_dev);
 scs_int scs_amd_linsys_sync(ScsLinSysWork *w);
+/* ---- blocks of right-hand sides: K solves of one KKT system at once (families of problems that share A, P and the cones) ----
+ * Column k of a block solve is what scs_solve_lin_sys(w, B[:, k], S[:, k], tol[k]) computes: the recurrence of
+ * linsys/cpu/indirect/private.c:133-217 (`pcg`) under the wrapper of :284-324, applied to that column alone -- its own alpha,
+ * beta, z'r, |r|_inf and tolerance, the strict `norm_r < tol` stop test, the max(tol, 1e-12) test before the first iteration
+ * (:163), the z'r == 0 breakdown exit, the cap of 10 n iterations (:307) and the zero short-circuit (:296-299); iterations are
+ * counted as the reference counts them (:203, :216).  The columns run in lock step on the device but share nothing except the
+ * workspace's A, P and diag_r: this is K independent conjugate-gradient solves, not block CG, and the bits of a column do not
+ * depend on the other columns of the block nor on its position in it.  A column that has stopped is frozen while the others go
+ * on.  Deterministic: two calls on the same inputs return the same bits.
+ * Device layout of a block of K columns: row-major, element (i, k) at i * W + k, W = scs_amd_linsys_multi_width(K) = the smallest
+ * of {2, 4, 8, 16} that is >= K; padding columns are zero.  One column goes to the single-vector path (bit-identical to
+ * scs_solve_lin_sys); more than 16 are served in chunks of at most 16.  The block buffers (7 n W + 2 m W values at the largest W
+ * used; 6 n W + 2 m W without P) are allocated at the first block call and freed by scs_free_lin_sys_work.
+ * scs_update_lin_sys_diag_r applies to block solves as to single ones.  Row-sharded systems (ScsAmdShard) have no block entry.
+ * ScsAmdStats: a block solve adds every column's iterations to cg_iters, one per column to lin_sys_solves, and one per block
+ * product that did work to mat_vecs (the largest iteration count of the block, plus one for a warm start). */
+/* K solves of scs_solve_lin_sys (private.c:284-324) on one workspace.  B: host, column-major, nrhs columns of
+ * length n + m, leading dimension ldb >= n + m; column k in: [r_x; r_y], out: [x; y].
+ * S: warm starts, n x nrhs, leading dimension lds >= n, or NULL (all cold).
+ * tol: nrhs tolerances.  iters: nrhs PCG iteration counts on return, or NULL.
+ * 0 on success; -1 on bad arguments (checked before any device call) or on a HIP failure (message on stderr; the workspace
+ * stays usable). */
+scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B, scs_int ldb,
+                                    const scs_float *S, scs_int lds, const scs_float *tol,
+                                    scs_int *iters);
+/* width of the device layout for nrhs columns (2, 4, 8 or 16; 1 for nrhs == 1; 0 if nrhs < 1 or > 16) */
+scs_int scs_amd_linsys_multi_width(scs_int nrhs);
+/* the operator pieces of scs_amd_linsys_mat_vec_dev / _mul_a_dev / _mul_at_dev (private.c:106-119; linsys/scs_matrix.c:161-186)
+ * on blocks in the device layout (row-major, width = scs_amd_linsys_multi_width(nrhs)); same stream contract.  All `width`
+ * columns of the output are written (a padding column holds the product of the input's padding column).  -1 for nrhs outside
+ * 1 .. 16; nrhs == 1 is the single-vector entry. */
+scs_int scs_amd_linsys_mat_vec_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev);
+scs_int scs_amd_linsys_mul_a_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev);
+scs_int scs_amd_linsys_mul_at_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *Y_dev, scs_float *X_dev);
 /* the SpMV kernel these entries (and scs_solve_lin_sys) run for A (which = 0) / A' (which = 1): the strings of
  * scs_amd_get_spmv_kernel_name.  Returns the length needed. */
 scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap);

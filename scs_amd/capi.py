@@ -145,6 +145,16 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             fn = getattr(lib, nm)
             fn.restype = scs_int
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # device pointers
+        # blocks of right-hand sides (include/scs_amd.h, B1 section); with the other scs_amd_linsys_* entries: the `linsys` branch also
+        # binds the reference backend, which has the five plugin functions only
+        lib.scs_amd_solve_lin_sys_multi.restype = scs_int
+        lib.scs_amd_solve_lin_sys_multi.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, fp, T.ip]
+        lib.scs_amd_linsys_multi_width.restype = scs_int
+        lib.scs_amd_linsys_multi_width.argtypes = [scs_int]
+        for nm in ("scs_amd_linsys_mat_vec_multi_dev", "scs_amd_linsys_mul_a_multi_dev", "scs_amd_linsys_mul_at_multi_dev"):
+            fn = getattr(lib, nm)
+            fn.restype = scs_int
+            fn.argtypes = [C.c_void_p, scs_int, C.c_void_p, C.c_void_p]  # device pointers
         lib.scs_amd_linsys_sync.restype = scs_int
         lib.scs_amd_linsys_sync.argtypes = [C.c_void_p]
         lib.scs_amd_linsys_spmv_kernel_name.restype = scs_int

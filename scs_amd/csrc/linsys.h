@@ -6,6 +6,7 @@
 #include "spmv.h"
 #include "scs_host.h"
 #include "spmv_wave.h"
+#include "spmm.h"
 
 namespace scsamd {
 
@@ -22,6 +23,31 @@ struct CgCtl {
   int cg_done;   // converged (or breakdown): remaining iteration kernels return
   int iters;     // PCG iterations performed (reference counting, private.c:203,216)
   int max_its;   // 10 n (private.c:307): the device stops there even if more iterations were enqueued
+};
+
+// Control block of a block solve (linsys_multi.h): what CgCtl holds, per column, plus one word that says every column has stopped.
+struct CgCtlM {
+  real ztr[2][MULTI_W_MAX];
+  real norm_r[MULTI_W_MAX], tol[MULTI_W_MAX], rhs_norm[MULTI_W_MAX];
+  int zero_rhs[MULTI_W_MAX]; // also set for the padding columns
+  int done[MULTI_W_MAX];     // this column has stopped: frozen from here on
+  int iters[MULTI_W_MAX];
+  int max_its;
+  int all_done; // every column has stopped: iteration kernels enqueued past this point return at once
+};
+
+// Buffers of the block solves, in the block layout of spmm.h at the largest width W used so far: 7 n W + 2 m W values
+// (6 n W + 2 m W without P).  Allocated at the first block call, reused, freed with the workspace.
+struct MultiWork {
+  int width = 0;    // width the buffers were allocated for (0: not allocated)
+  int last_its = 16;
+  DevBuf<real> bx, by;      // right-hand side / solution: n W, m W
+  DevBuf<real> s, r, z, p;  // n W each
+  DevBuf<real> gt;          // (n + m) W: Gp (n W) and tmp (m W) during a solve; the column-major staging of the host block around it
+  DevBuf<real> Pp;          // n W, only with P
+  DevBuf<real> part_pgp, part_ztr, part_max; // per-workgroup, per-column reduction partials
+  DevBuf<CgCtlM> ctl;
+  PinnedBuf<CgCtlM> hctl;
 };
 
 // ONE linear system split by rows of A over several devices (the operator split is
@@ -110,6 +136,12 @@ struct LinSys {
   void mul_A(const real *x_n, real *y_m);  // y = A x
   void mul_At(const real *y_m, real *x_n); // x = A' y
   void mul_P(const real *x_n, real *y_n);  // y = P x (full symmetric)
+  // ---- blocks of right-hand sides (linsys_multi.h) ----
+  MultiWork *multi = nullptr; // owned
+  void ensure_multi(int W);
+  void launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip);
+  void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr);
+  void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
   long long matvec_bytes() const { return A.algorithmic_bytes() + At.algorithmic_bytes(); }
   void harvest_timers();
 

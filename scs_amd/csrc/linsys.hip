@@ -838,6 +838,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_linsys_fused(CsrView A, CsrVi
 // ----------------------------------------------------------------------------
 LinSys::~LinSys() {
   if (cg_graph) (void)hipGraphExecDestroy(cg_graph);
+  delete multi;
   if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -1428,6 +1429,8 @@ int LinSys::solve_dev(real *b, const real *s, real tol, const real *warm_part, i
 
 } // namespace scsamd
 
+#include "linsys_multi.h" // blocks of right-hand sides: K solves in lock step
+
 // ============================================================================
 // B1: the reference's linear-system plugin ABI (include/linsys.h:25-71)
 // ============================================================================
@@ -1530,6 +1533,17 @@ ScsLinSysWork *scs_init_lin_sys_work(const ScsMatrix *A, const ScsMatrix *P, con
   return w;
 }
 
+// one solve through the staging buffers of the host-pointer boundary; returns the PCG iteration count
+static int solve_one_host(LinSys &ls, scs_float *b, const scs_float *s, scs_float tol) {
+  const size_t n = ls.n, m = ls.m;
+  ls.b_stage.upload(b, n + m, ls.stream);
+  if (s) ls.s_stage.upload(s, n, ls.stream);
+  const int its = ls.solve_dev(ls.b_stage.p, s ? ls.s_stage.p : nullptr, tol);
+  ls.b_stage.download(b, n + m, ls.stream);
+  HIP_CHECK(hipStreamSynchronize(ls.stream));
+  return its;
+}
+
 scs_int scs_solve_lin_sys(ScsLinSysWork *w, scs_float *b, const scs_float *s, scs_float tol) {
   if (!w || !b) return -1;
   if (tol <= 0.) {
@@ -1538,15 +1552,60 @@ scs_int scs_solve_lin_sys(ScsLinSysWork *w, scs_float *b, const scs_float *s, sc
   }
   try {
     HIP_CHECK(hipSetDevice(w->device));
-    LinSys &ls = w->ls;
-    const size_t n = ls.n, m = ls.m;
-    ls.b_stage.upload(b, n + m, ls.stream);
-    if (s) ls.s_stage.upload(s, n, ls.stream);
-    ls.solve_dev(ls.b_stage.p, s ? ls.s_stage.p : nullptr, tol);
-    ls.b_stage.download(b, n + m, ls.stream);
-    HIP_CHECK(hipStreamSynchronize(ls.stream));
+    solve_one_host(w->ls, b, s, tol);
   } catch (const std::exception &ex) {
     fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
+}
+
+// ---- blocks of right-hand sides: K solves of scs_solve_lin_sys (private.c:284-324) on one workspace ----
+scs_int scs_amd_linsys_multi_width(scs_int nrhs) { return (scs_int)multi_width((long long)nrhs); }
+
+scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B, scs_int ldb, const scs_float *S, scs_int lds,
+                                    const scs_float *tol, scs_int *iters) {
+  if (!w || !B || !tol || nrhs < 1) return -1;
+  LinSys &ls = w->ls;
+  const size_t n = ls.n, m = ls.m, sz = sizeof(real);
+  if ((long long)ldb < (long long)(n + m) || (S && (long long)lds < (long long)n)) return -1;
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    if (ls.shard) throw HipError("scs_amd: block solves are not available on a row-sharded workspace");
+    for (scs_int c0 = 0; c0 < nrhs; c0 += MULTI_W_MAX) { // chunks of at most 16 columns
+      const int K = (int)std::min<scs_int>(MULTI_W_MAX, nrhs - c0);
+      scs_float *Bc = B + (size_t)c0 * (size_t)ldb;
+      const scs_float *Sc = S ? S + (size_t)c0 * (size_t)lds : nullptr;
+      if (K == 1) { // the single-vector path, bit for bit
+        const int its = solve_one_host(ls, Bc, Sc, tol[c0]);
+        if (iters) iters[c0] = its;
+        continue;
+      }
+      const int W = multi_width(K);
+      ls.ensure_multi(W);
+      MultiWork &mw = *ls.multi;
+      const int g = vec_grid((long long)(n + m));
+      if (Sc) { // staged column-major in z, transposed into s on the device
+        HIP_CHECK(hipMemcpy2DAsync(mw.z.p, n * sz, Sc, (size_t)lds * sz, n * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
+        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.z.p, mw.s.p, (int)n,
+                                             (real *)nullptr, 0, K));
+      }
+      HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, Bc, (size_t)ldb * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
+                                           (int)m, K));
+      int its[MULTI_W_MAX];
+      ls.solve_multi_dev(K, W, Sc != nullptr, tol + c0, its);
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
+                                           (int)m, K));
+      HIP_CHECK(hipMemcpy2DAsync(Bc, (size_t)ldb * sz, mw.gt.p, (n + m) * sz, (n + m) * sz, (size_t)K, hipMemcpyDeviceToHost, ls.stream));
+      HIP_CHECK(hipStreamSynchronize(ls.stream));
+      HIP_CHECK(hipGetLastError());
+      if (iters)
+        for (int k = 0; k < K; ++k) iters[c0 + k] = its[k];
+    }
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(ls.stream); // nothing of this call may still be reading or writing the caller's block
     return -1;
   }
   return 0;
@@ -1592,6 +1651,38 @@ scs_int scs_amd_linsys_mul_a_dev(ScsLinSysWork *w, const scs_float *x_dev, scs_f
 }
 scs_int scs_amd_linsys_mul_at_dev(ScsLinSysWork *w, const scs_float *y_dev, scs_float *x_dev) {
   return with_work(w, y_dev, x_dev, [](LinSys &ls, const real *y, real *x) { ls.mul_At(y, x); });
+}
+// the same pieces on blocks in the device layout of spmm.h
+static scs_int with_work_multi(ScsLinSysWork *w, scs_int nrhs, const void *a, const void *b, void (*fn)(LinSys &, int, const real *, real *),
+                               void (*fn1)(LinSys &, const real *, real *)) {
+  if (!w || !a || !b) return -1;
+  const int W = multi_width((long long)nrhs);
+  if (W == 0) return -1;
+  if (W == 1) return with_work(w, a, b, fn1);
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    w->ls.ensure_multi(W);
+    fn(w->ls, W, static_cast<const real *>(a), static_cast<real *>(const_cast<void *>(b)));
+    HIP_CHECK(hipGetLastError());
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
+}
+scs_int scs_amd_linsys_mat_vec_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev) {
+  return with_work_multi(w, nrhs, X_dev, Y_dev, [](LinSys &ls, int W, const real *x, real *y) { ls.mat_vec_multi_dev(W, x, y, nullptr); },
+                         [](LinSys &ls, const real *x, real *y) { ls.mat_vec_dev(x, y, nullptr); });
+}
+scs_int scs_amd_linsys_mul_a_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev) {
+  return with_work_multi(w, nrhs, X_dev, Y_dev, [](LinSys &ls, int W, const real *x, real *y) {
+    EpiArgs e{nullptr, nullptr, nullptr, nullptr};
+    ls.launch_spmm(W, EPI_PLAIN, ls.A, x, y, e, nullptr, nullptr); }, [](LinSys &ls, const real *x, real *y) { ls.mul_A(x, y); });
+}
+scs_int scs_amd_linsys_mul_at_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *Y_dev, scs_float *X_dev) {
+  return with_work_multi(w, nrhs, Y_dev, X_dev, [](LinSys &ls, int W, const real *y, real *x) {
+    EpiArgs e{nullptr, nullptr, nullptr, nullptr};
+    ls.launch_spmm(W, EPI_PLAIN, ls.At, y, x, e, nullptr, nullptr); }, [](LinSys &ls, const real *y, real *x) { ls.mul_At(y, x); });
 }
 // the SpMV kernel the workspace runs for A (which = 0) / A' (which = 1): the strings of scs_amd_get_spmv_kernel_name
 scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap) {

@@ -1,0 +1,382 @@
+// linsys_multi.h -- K independent Jacobi-PCG solves of the reduced KKT system in lock step on one workspace (part of
+// linsys.hip: included there, behind the single-vector solve whose helpers it uses).
+//
+// Column k computes what LinSys::solve_dev computes for that column alone: the recurrence of reference
+// linsys/cpu/indirect/private.c:133-217 and the wrapper :284-324, with its OWN alpha, beta, z'r, |r|_inf, tolerance, stop
+// tests, breakdown exit, iteration cap and zero short-circuit.  Nothing couples the columns (this is not block CG): every
+// reduction runs over the lanes and workgroup partials of one column only, in an order that does not depend on the column's
+// position, so the bits of a column do not depend on its neighbours.  A column that has stopped is frozen: its lanes return
+// before they load anything, its x is not touched again and it counts no more iterations.  When every column has stopped the
+// all_done word is set, and iteration kernels that were enqueued past that point return at their first instruction.
+//
+// One plain form of the iteration (the four kernels of linsys.hip's header comment, on blocks):
+//   csr_block<DIV>  tmp = R_y^-1 (A p)            csr_block<GP>  Gp = R_x p + P p + A' tmp, partials of p'Gp per column
+//   k_m_cg_update   alpha; x, r, z; partials      k_m_cg_direction  stop tests; beta; p; control block
+// Buffers (MultiWork, linsys.h): 7 n W + 2 m W values at the largest width used (6 n W + 2 m W without P), allocated at the
+// first block call, reused, freed with the workspace.
+#pragma once
+
+namespace scsamd {
+
+struct TolArgs {
+  real t[MULTI_W_MAX];
+};
+
+// consumer side of the two-level reduction, per column: `part` holds count x W entries, entry (b, k) at b * W + k
+template <int W> __device__ __forceinline__ real reduce_partials_col_sum(const real *part, int count, real *sh) {
+  real s = 0;
+  for (int i = threadIdx.x; i < count * W; i += SCSAMD_BLOCK) s += part[i]; // SCSAMD_BLOCK % W == 0: a thread stays in its column
+  return block_col_sum<W>(s, sh);
+}
+template <int W> __device__ __forceinline__ real reduce_partials_col_max(const real *part, int count, real *sh) {
+  real s = 0;
+  for (int i = threadIdx.x; i < count * W; i += SCSAMD_BLOCK) {
+    const real v = part[i];
+    s = v > s ? v : s;
+  }
+  return block_col_max<W>(s, sh);
+}
+
+// column-major (len x K, leading dimension len) <-> block layout; padding columns become zero
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_to_block(const real *__restrict__ src, real *dx, int n, real *dy, int m, int K) {
+  const int len = n + m;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) {
+    real *d = i < n ? dx + (size_t)i * W : dy + (size_t)(i - n) * W;
+#pragma unroll
+    for (int k = 0; k < W; ++k) d[k] = k < K ? src[(size_t)k * len + i] : (real)0;
+  }
+}
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_from_block(real *dst, const real *__restrict__ sx, int n, const real *__restrict__ sy, int m, int K) {
+  const int len = n + m;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) {
+    const real *s = i < n ? sx + (size_t)i * W : sy + (size_t)(i - n) * W;
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+      if (k < K) dst[(size_t)k * len + i] = s[k];
+  }
+}
+
+// |[r_x; r_y]|_inf per column (private.c:296)
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_absmax(const real *__restrict__ bx, size_t nx, const real *__restrict__ by, size_t ny, real *part) {
+  __shared__ real red[4 * W];
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x; // gs % W == 0
+  real mx = 0;
+  for (size_t f = gtid; f < nx; f += gs) {
+    const real a = absval(bx[f]);
+    mx = a > mx ? a : mx;
+  }
+  for (size_t f = gtid; f < ny; f += gs) {
+    const real a = absval(by[f]);
+    mx = a > mx ? a : mx;
+  }
+  mx = block_col_max<W>(mx, red);
+  if (threadIdx.x < W) part[(size_t)blockIdx.x * W + threadIdx.x] = mx;
+}
+
+// block 0 of a control kernel: every column stopped?
+__device__ __forceinline__ void set_all_done(CgCtlM *ctl, int W, bool col_done) {
+  if (threadIdx.x < 64) {
+    const unsigned long long live = __ballot((int)threadIdx.x < W && !col_done);
+    if (threadIdx.x == 0) ctl->all_done = live == 0 ? 1 : 0;
+  }
+}
+
+// private.c:296-303 per column: zero short-circuit, tmp = R_y^-1 r_y; arms the control block.  Padding columns count as zero.
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by, const real *__restrict__ ry, real *tmp, int n, int m,
+                                                             const real *part, int pcount, CgCtlM *ctl, TolArgs tol, int K, int max_its) {
+  __shared__ real red[4 * W];
+  const real nb = reduce_partials_col_max<W>(part, pcount, red);
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
+  const int col = threadIdx.x & (W - 1);
+  const bool zero = col >= K || nb <= (real)1e-12;
+  if (zero) {
+    for (size_t f = gtid; f < (size_t)n * W; f += gs) bx[f] = 0;
+    for (size_t f = gtid; f < (size_t)m * W; f += gs) {
+      by[f] = 0;
+      tmp[f] = 0;
+    }
+  } else {
+    for (size_t f = gtid; f < (size_t)m * W; f += gs) tmp[f] = by[f] / ry[f / W];
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < W) {
+      ctl->zero_rhs[col] = zero ? 1 : 0;
+      ctl->done[col] = zero ? 1 : 0;
+      ctl->iters[col] = 0;
+      ctl->tol[col] = col < K ? tol.t[col] : (real)0;
+      ctl->rhs_norm[col] = nb;
+      ctl->norm_r[col] = 0;
+      ctl->ztr[0][col] = 0;
+      ctl->ztr[1][col] = 0;
+    }
+    if (threadIdx.x == 0) ctl->max_its = max_its;
+    set_all_done(ctl, W, zero);
+  }
+}
+
+// private.c:145-172 per column
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_init(real *x, const real *__restrict__ s, real *r, real *z, const real *__restrict__ M, int n,
+                                                            real *part_ztr, real *part_max, const CgCtlM *ctl) {
+  __shared__ real red[4 * W];
+  if (ctl->all_done) return;
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
+  const int col = threadIdx.x & (W - 1);
+  real ztr = 0, mx = 0;
+  if (!ctl->zero_rhs[col]) {
+    for (size_t f = gtid; f < (size_t)n * W; f += gs) {
+      real ri;
+      if (s) {
+        ri = x[f] - r[f]; // r held G s; r = b - G s
+        x[f] = s[f];
+      } else {
+        ri = x[f];
+        x[f] = 0;
+      }
+      r[f] = ri;
+      const real zi = ri * M[f / W];
+      z[f] = zi;
+      ztr += zi * ri;
+      const real a = absval(ri);
+      mx = a > mx ? a : mx;
+    }
+  }
+  ztr = block_col_sum<W>(ztr, red);
+  mx = block_col_max<W>(mx, red);
+  if (threadIdx.x < W) {
+    part_ztr[(size_t)blockIdx.x * W + threadIdx.x] = ztr;
+    part_max[(size_t)blockIdx.x * W + threadIdx.x] = mx;
+  }
+}
+
+// private.c:163 early-out with max(tol, 1e-12) per column; p = z
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_start(real *p, const real *__restrict__ z, int n, const real *part_ztr, const real *part_max,
+                                                             int pcount, CgCtlM *ctl) {
+  __shared__ real red[4 * W];
+  if (ctl->all_done) return;
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
+  const int col = threadIdx.x & (W - 1);
+  const int zero = ctl->zero_rhs[col];
+  const real tol = ctl->tol[col];
+  const real ztr = reduce_partials_col_sum<W>(part_ztr, pcount, red);
+  const real nr = reduce_partials_col_max<W>(part_max, pcount, red);
+  const real thr = tol > (real)1e-12 ? tol : (real)1e-12;
+  const bool conv = nr < thr;
+  if (!zero && !conv)
+    for (size_t f = gtid; f < (size_t)n * W; f += gs) p[f] = z[f];
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < W && !zero) {
+      ctl->ztr[0][col] = ztr;
+      ctl->norm_r[col] = nr;
+      if (conv) ctl->done[col] = 1;
+    }
+    set_all_done(ctl, W, zero || conv);
+  }
+}
+
+// private.c:181-197 per column
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_update(real *x, real *r, real *z, const real *__restrict__ p, const real *__restrict__ Gp,
+                                                              const real *__restrict__ M, int n, const real *part_pgp, int cnt_pgp,
+                                                              real *part_ztr, real *part_max, const CgCtlM *ctl, int parity) {
+  __shared__ real red[4 * W];
+  if (ctl->all_done) return;
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
+  const int col = threadIdx.x & (W - 1);
+  const int done = ctl->done[col];
+  const real ztr_in = ctl->ztr[parity][col];
+  const real pgp = reduce_partials_col_sum<W>(part_pgp, cnt_pgp, red);
+  real ztr = 0, mx = 0;
+  if (!done) {
+    const real alpha = ztr_in / pgp;
+    for (size_t f = gtid; f < (size_t)n * W; f += gs) {
+      x[f] += alpha * p[f];
+      const real ri = r[f] + (-alpha) * Gp[f];
+      r[f] = ri;
+      const real zi = ri * M[f / W];
+      z[f] = zi;
+      ztr += zi * ri;
+      const real a = absval(ri);
+      mx = a > mx ? a : mx;
+    }
+  }
+  ztr = block_col_sum<W>(ztr, red);
+  mx = block_col_max<W>(mx, red);
+  if (threadIdx.x < W) {
+    part_ztr[(size_t)blockIdx.x * W + threadIdx.x] = ztr;
+    part_max[(size_t)blockIdx.x * W + threadIdx.x] = mx;
+  }
+}
+
+// private.c:202-214 per column
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_direction(real *p, const real *__restrict__ z, int n, const real *part_ztr,
+                                                                 const real *part_max, int pcount, CgCtlM *ctl, int parity) {
+  __shared__ real red[4 * W];
+  if (ctl->all_done) return;
+  const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
+  const int col = threadIdx.x & (W - 1);
+  const int done = ctl->done[col];
+  const real ztr_prev = ctl->ztr[parity][col], tol = ctl->tol[col];
+  const int its = ctl->iters[col], max_its = ctl->max_its;
+  const real ztr = reduce_partials_col_sum<W>(part_ztr, pcount, red);
+  const real nr = reduce_partials_col_max<W>(part_max, pcount, red);
+  const bool conv = nr < tol;
+  const bool brk = !conv && ztr_prev == (real)0;
+  if (!done && !conv && !brk) {
+    const real beta = ztr / ztr_prev;
+    for (size_t f = gtid; f < (size_t)n * W; f += gs) p[f] = z[f] + beta * p[f];
+  }
+  if (blockIdx.x == 0) {
+    bool stop = done != 0;
+    if (threadIdx.x < W && !done) {
+      const int it2 = brk ? its : its + 1; // converged at i -> i + 1; breakdown returns i (private.c:203,216)
+      ctl->ztr[parity ^ 1][col] = ztr;
+      ctl->norm_r[col] = nr;
+      ctl->iters[col] = it2;
+      stop = conv || brk || it2 >= max_its;
+      if (stop) ctl->done[col] = 1;
+    }
+    set_all_done(ctl, W, stop);
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+template <int W>
+static void launch_spmm_w(int epi, int g, hipStream_t st, const CsrView &v, const real *X, real *Y, const EpiArgs &e, const int *cskip,
+                          const int *allskip) {
+  switch (epi) {
+  case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+  case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+  case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+  case EPI_ACC: hipLaunchKernelGGL((csr_block_kernel<W, EPI_ACC>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+  case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+  default: throw HipError("scs_amd: bad block-product epilogue");
+  }
+}
+
+#define MULTI_DISPATCH(W_, CALL)                                                                                       \
+  do {                                                                                                                 \
+    switch (W_) {                                                                                                      \
+    case 2: { constexpr int MW = 2; CALL; } break;                                                                     \
+    case 4: { constexpr int MW = 4; CALL; } break;                                                                     \
+    case 8: { constexpr int MW = 8; CALL; } break;                                                                     \
+    case 16: { constexpr int MW = 16; CALL; } break;                                                                   \
+    default: throw HipError("scs_amd: bad block width");                                                               \
+    }                                                                                                                  \
+  } while (0)
+
+void LinSys::launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip) {
+  const int g = spmm_grid(mat.rows, W);
+  const CsrView v = mat.view();
+  MULTI_DISPATCH(W, launch_spmm_w<MW>(epi, g, stream, v, X, Y, e, cskip, allskip));
+  n_spmv++;
+}
+
+void LinSys::ensure_multi(int W) {
+  if (shard) throw HipError("scs_amd: block solves are not available on a row-sharded workspace");
+  if (!multi) multi = new MultiWork();
+  MultiWork &mw = *multi;
+  if (mw.width >= W) return;
+  mw.width = 0; // a failed allocation below leaves a state that is built again at the next call
+  const size_t nw = (size_t)n * W, mwid = (size_t)m * W;
+  mw.bx.alloc(nw);
+  mw.by.alloc(mwid);
+  mw.s.alloc(nw);
+  mw.r.alloc(nw);
+  mw.z.alloc(nw);
+  mw.p.alloc(nw);
+  mw.gt.alloc(nw + mwid);
+  if (has_P) mw.Pp.alloc(nw);
+  mw.part_pgp.alloc((size_t)SPMM_MAX_GRID * MULTI_W_MAX);
+  mw.part_ztr.alloc((size_t)PART_CAP / 2 * MULTI_W_MAX);
+  mw.part_max.alloc((size_t)PART_CAP / 2 * MULTI_W_MAX);
+  if (!mw.ctl.p) mw.ctl.alloc(1);
+  if (!mw.hctl.p) mw.hctl.alloc(1);
+  mw.width = W;
+}
+
+// G X on blocks (private.c:106-119 per column); dot_partials as in launch_spmm's EPI_GP
+void LinSys::mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip) {
+  MultiWork &mw = *multi;
+  real *tmpb = mw.gt.p + (size_t)n * mw.width;
+  EpiArgs e1{ry.p, nullptr, nullptr, nullptr};
+  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip);
+  if (has_P) {
+    EpiArgs ep{nullptr, nullptr, nullptr, nullptr};
+    launch_spmm(W, EPI_PLAIN, P, X, mw.Pp.p, ep, cskip, allskip);
+  }
+  EpiArgs e2{rx.p, X, has_P ? mw.Pp.p : nullptr, dot_partials};
+  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip);
+  n_matvecs++;
+}
+
+// K columns (2 <= K <= W) held in multi->bx / by (and multi->s when warm) in the block layout: [r_x; r_y] -> [x; y] in place
+void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out) {
+  MultiWork &mw = *multi;
+  const int gv = vec_grid((long long)n * W), gnm = vec_grid(((long long)n + m) * W);
+  CgCtlM *c = mw.ctl.p;
+  real *Gp = mw.gt.p, *tmpb = mw.gt.p + (size_t)n * mw.width;
+  const int *zero = c->zero_rhs, *done = c->done, *all = &c->all_done;
+  const int max_its = (int)std::min<long long>(10LL * n, 2147483647LL); // private.c:307
+  TolArgs ta{};
+  for (int k = 0; k < K; ++k) ta.t[k] = tolv[k];
+  const size_t nx = (size_t)n * W, ny = (size_t)m * W;
+  const long long mv0 = n_matvecs;
+
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_absmax<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, nx, mw.by.p, ny, mw.part_max.p));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rhs_prep<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, mw.by.p, ry.p, tmpb, n, m,
+                                       mw.part_max.p, gnm, c, ta, K, max_its));
+  { // b_x += A' R_y^-1 r_y   (private.c:305)
+    EpiArgs e{nullptr, nullptr, nullptr, nullptr};
+    launch_spmm(W, EPI_ACC, At, tmpb, mw.bx.p, e, zero, all);
+  }
+  if (warm) mat_vec_multi_dev(W, mw.s.p, mw.r.p, nullptr, zero, all); // r = G s  (private.c:153)
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_init<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, warm ? mw.s.p : nullptr, mw.r.p,
+                                       mw.z.p, M.p, n, mw.part_ztr.p, mw.part_max.p, c));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_start<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
+                                       mw.part_max.p, gv, c));
+  // iteration batches: one control record read per batch, as in solve_dev
+  const int gp = spmm_grid(At.rows, W);
+  long long it = 0;
+  int batch = std::max(4, std::min(mw.last_its + 1, 4096));
+  for (;;) {
+    int nb = (int)std::min<long long>(batch, (long long)max_its - it);
+    if (nb < 1) nb = 1;
+    for (int j = 0; j < nb; ++j) {
+      const int q = (int)((it + j) & 1);
+      mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all);
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_update<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, mw.r.p, mw.z.p, mw.p.p, Gp,
+                                           M.p, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_direction<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
+                                           mw.part_max.p, gv, c, q));
+    }
+    it += nb;
+    HIP_CHECK(hipMemcpyAsync(mw.hctl.p, c, sizeof(CgCtlM), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (mw.hctl.p->all_done || it >= max_its) break;
+    batch = std::max(4, std::min(mw.last_its / 4 + 1, 1024));
+  }
+  { // y = R_y^-1 (A x - r_y)   (private.c:313-317)
+    EpiArgs e{ry.p, nullptr, nullptr, nullptr};
+    launch_spmm(W, EPI_NEGDIV, A, mw.bx.p, mw.by.p, e, zero, nullptr);
+  }
+  HIP_CHECK(hipGetLastError());
+  int most = 0;
+  for (int k = 0; k < K; ++k) {
+    const int its = mw.hctl.p->iters[k];
+    if (iters_out) iters_out[k] = its;
+    tot_cg_its += its;
+    most = std::max(most, its);
+  }
+  mw.last_its = most;
+  n_solves += K;
+  n_matvecs = mv0 + most + (warm ? 1 : 0); // a block product counts once; products enqueued past the last stop did nothing
+}
+
+} // namespace scsamd

@@ -1,0 +1,130 @@
+"""`LinSys` -- the linear-system workspace of the plugin ABI (include/scs_amd.h, B1) as a Python object.
+
+Solves the reduced KKT system of SCS on the GPU,
+
+    (R_x + P + A' R_y^-1 A) x = r_x + A' R_y^-1 r_y ,   y = R_y^-1 (A x - r_y)
+
+for one right-hand side (`solve`, scs_solve_lin_sys) or for a block of them at once (`solve_many`,
+scs_amd_solve_lin_sys_multi: K independent PCG solves in lock step that share A, P and diag_r).  One workspace lives for the
+lifetime of the object (scs_init_lin_sys_work once, scs_free_lin_sys_work on close / garbage collection).  Host code only: every
+flop is in the library.
+
+A      : scipy sparse, m x n
+diag_r : [R_x (n); R_y (m)], positive
+P      : n x n symmetric or None; the upper triangle is used, as the C API requires
+dtype  : "f64" (default) or "f32" (the SFLOAT library)
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+
+def check_block(n, m, B, S=None, tol=1e-9):
+    """Shapes of a block solve, checked before the library is called (needs no workspace): B (n + m, K), S None or (n, K),
+    tol a positive scalar or K of them.  Returns K."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.shape[0] != n + m or B.shape[1] < 1:
+        raise ValueError(f"B must have shape ({n + m}, K) with K >= 1, got {B.shape}")
+    K = B.shape[1]
+    if S is not None:
+        S = np.asarray(S)
+        if S.ndim != 2 or S.shape != (n, K):
+            raise ValueError(f"S must have shape ({n}, {K}), got {S.shape}")
+    t = np.asarray(tol, dtype=np.float64)
+    if t.ndim > 1 or (t.ndim == 1 and t.shape[0] != K):
+        raise ValueError(f"tol must be a scalar or have length {K}, got shape {t.shape}")
+    if not np.all(t > 0):
+        raise ValueError("tol must be positive")
+    return K
+
+
+class LinSys:
+    def __init__(self, A, diag_r, P=None, dtype="f64"):
+        self._w = None
+        self._lib = capi.load("libscsamd_f32.so" if dtype in ("f32", np.float32) else "libscsamd.so")
+        T = self._T = self._lib._scs_types
+        import scipy.sparse as sp
+        A = sp.csc_matrix(A)
+        self.m, self.n = A.shape
+        diag_r = np.ascontiguousarray(diag_r, dtype=T.np_float)
+        if diag_r.shape != (self.n + self.m,):
+            raise ValueError("diag_r has the wrong length")
+        if P is not None and sp.csc_matrix(P).shape != (self.n, self.n):
+            raise ValueError("P has the wrong shape")
+        self._prob = capi.Problem(A, np.zeros(self.m), np.zeros(self.n), dict(l=self.m), P=P, T=T)  # owns the arrays behind the pointers
+        self._w = self._lib.scs_init_lin_sys_work(C.byref(self._prob.matA), C.byref(self._prob.matP) if self._prob.matP is not None else None,
+                                                  diag_r.ctypes.data_as(T.fp))
+        if not self._w:
+            raise ValueError("ScsLinSysWork allocation error!")
+
+    def _work(self):
+        if not self._w:
+            raise RuntimeError("workspace was closed")
+        return self._w
+
+    def solve(self, b, s=None, tol=1e-9):
+        """scs_solve_lin_sys: b = [r_x; r_y] -> [x; y]; s = warm start for x (n) or None."""
+        w, T = self._work(), self._T
+        b = np.asarray(b)
+        if b.shape != (self.n + self.m,):
+            raise ValueError("b has the wrong length")
+        if s is not None and np.asarray(s).shape != (self.n,):
+            raise ValueError("s has the wrong length")
+        if not tol > 0:
+            raise ValueError("tol must be positive")
+        out = np.array(b, dtype=T.np_float, order="C", copy=True)
+        sv = None if s is None else np.ascontiguousarray(s, dtype=T.np_float)
+        if self._lib.scs_solve_lin_sys(w, out.ctypes.data_as(T.fp), sv.ctypes.data_as(T.fp) if sv is not None else None, float(tol)) != 0:
+            raise RuntimeError("scs_solve_lin_sys failed")
+        return out
+
+    def solve_many(self, B, S=None, tol=1e-9):
+        """scs_amd_solve_lin_sys_multi: column k of B (n + m, K) -> [x; y] of that column, as `solve` would give it; S (n, K) warm
+        starts or None; tol a scalar or one per column.  Returns (XY, iters): the solutions (n + m, K) and the PCG iteration count
+        of every column.  B, S and tol are not modified."""
+        w, T = self._work(), self._T
+        K = check_block(self.n, self.m, B, S, tol)
+        out = np.array(B, dtype=T.np_float, order="F", copy=True)
+        Sv = None if S is None else np.asfortranarray(S, dtype=T.np_float)
+        tv = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, dtype=T.np_float), (K,)))
+        iters = np.zeros(K, dtype=T.np_int)
+        rc = self._lib.scs_amd_solve_lin_sys_multi(w, K, out.ctypes.data_as(T.fp), self.n + self.m,
+                                                   Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
+                                                   tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
+        if rc != 0:
+            raise RuntimeError("scs_amd_solve_lin_sys_multi failed")
+        return out, iters.astype(np.int64)
+
+    def update_diag_r(self, d):
+        """scs_update_lin_sys_diag_r: new [R_x; R_y]; applies to single and block solves alike."""
+        w, T = self._work(), self._T
+        d = np.ascontiguousarray(d, dtype=T.np_float)
+        if d.shape != (self.n + self.m,):
+            raise ValueError("diag_r has the wrong length")
+        if self._lib.scs_update_lin_sys_diag_r(w, d.ctypes.data_as(T.fp)) != 0:
+            raise RuntimeError("scs_update_lin_sys_diag_r failed")
+
+    def stats(self):
+        """ScsAmdStats of the workspace as a dict (cg_iters, lin_sys_solves, mat_vecs, ...)."""
+        st = self._T.ScsAmdStats()
+        self._lib.scs_amd_linsys_get_stats(self._work(), C.byref(st))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def close(self):
+        if self._w:
+            self._lib.scs_free_lin_sys_work(self._w)
+            self._w = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
