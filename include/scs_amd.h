@@ -236,6 +236,38 @@ scs_int scs_amd_cone_proj_dual(ScsAmdConeWork *c, scs_float *x,
                                const scs_float *r_y);
 /* replaces src/cones.c:338 (_scs_finish_cone) */
 void scs_amd_cone_finish(ScsAmdConeWork *c);
+/* ---- blocks of vectors: K projections at once (the cone half of an iteration over a family of problems that share the cones) ----
+ * Column k of a block projection is what scs_amd_cone_proj_dual(c, X[:, k], r_y) computes -- the Moreau wrapper of
+ * src/cones.c:1552-1596 around proj_cone (:1340-1394) -- for every cone scs_amd_cone_init accepts, to the projection's own
+ * accuracy (not bit for bit: the reduction trees of the second-order cones differ).  The columns share the cone description and
+ * r_y and nothing else: on a freshly initialised workspace the bits of a column do not depend on the other columns, nor, within
+ * one width, on its position; two runs on the same inputs return the same bits (no floating-point atomics).
+ * Device layout: that of the block solve (scs_amd_solve_lin_sys_multi) -- row-major, element (i, k) at i * W + k,
+ * W = scs_amd_cone_multi_width(nrhs).  All W columns are written; columns nrhs .. W - 1 come back zero.
+ * Carried state (the box cone's Newton start, src/cones.c:1560; each PSD block's eigenbasis; the periodic cold restart) belongs
+ * to the column position and passes from one block call to the next of the same width; a change of width starts cold.  Block
+ * calls neither read nor write the state of the single-vector path.  Block state and staging are allocated at the first block
+ * call and freed by scs_amd_cone_finish.  One column (nrhs == 1) IS the single-vector path, bit for bit. */
+/* width of the device layout for nrhs columns (2, 4, 8 or 16; 1 for nrhs == 1; 0 if nrhs < 1 or > 16) */
+scs_int scs_amd_cone_multi_width(scs_int nrhs);
+/* K projections of scs_amd_cone_proj_dual (src/cones.c:1552) on one workspace.  X: host, column-major, nrhs columns of length
+ * m, leading dimension ldx >= m; each column is overwritten by its projection onto the dual cone under the r_y metric; rows
+ * between m and ldx are not touched.  r_y: host, length m, shared by all columns, or NULL.  More than 16 columns are served in
+ * chunks of at most 16 (a last chunk of one column as a block of width 2: it stays off the single-vector state).
+ * 0 on success; 1 when a PSD block of any column hit the Jacobi sweep cap (as scs_amd_cone_proj_dual: reported, not fatal,
+ * src/cones.c:1031); -1 on bad arguments (checked before any device call; X untouched) or on a HIP failure (message on
+ * stderr; the workspace stays usable). */
+scs_int scs_amd_cone_proj_dual_multi(ScsAmdConeWork *c, scs_int nrhs, scs_float *X, scs_int ldx,
+                                     const scs_float *r_y);
+/* the same on DEVICE pointers, in place, under the stream contract of scs_amd_linsys_*_dev: the work is enqueued on the
+ * workspace's private stream; the caller synchronises its own work before the call and calls scs_amd_cone_sync before it reads
+ * the result.  x_dev: m values; X_dev: m * W values in the device layout; r_y_dev: m values or NULL.  -1 for nrhs outside
+ * 1 .. 16; nrhs == 1 is the single-vector entry.  PSD blocks that hit the sweep cap are counted on the device and reported by
+ * the next host-pointer projection. */
+scs_int scs_amd_cone_proj_dual_dev(ScsAmdConeWork *c, scs_float *x_dev, const scs_float *r_y_dev);
+scs_int scs_amd_cone_proj_dual_multi_dev(ScsAmdConeWork *c, scs_int nrhs, scs_float *X_dev,
+                                         const scs_float *r_y_dev);
+scs_int scs_amd_cone_sync(ScsAmdConeWork *c);
 
 /* ======================= instrumentation ================================== */
 /* Not in the reference (its `tot_cg_its`, private.h:28, is never surfaced).

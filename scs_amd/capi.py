@@ -136,6 +136,17 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
         lib.scs_amd_cone_proj_dual.argtypes = [C.c_void_p, fp, fp]
         lib.scs_amd_cone_finish.restype = None
         lib.scs_amd_cone_finish.argtypes = [C.c_void_p]
+        # blocks of vectors (include/scs_amd.h, B1' section)
+        lib.scs_amd_cone_multi_width.restype = scs_int
+        lib.scs_amd_cone_multi_width.argtypes = [scs_int]
+        lib.scs_amd_cone_proj_dual_multi.restype = scs_int
+        lib.scs_amd_cone_proj_dual_multi.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp]
+        lib.scs_amd_cone_proj_dual_dev.restype = scs_int
+        lib.scs_amd_cone_proj_dual_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # device pointers
+        lib.scs_amd_cone_proj_dual_multi_dev.restype = scs_int
+        lib.scs_amd_cone_proj_dual_multi_dev.argtypes = [C.c_void_p, scs_int, C.c_void_p, C.c_void_p]
+        lib.scs_amd_cone_sync.restype = scs_int
+        lib.scs_amd_cone_sync.argtypes = [C.c_void_p]
     if stats:
         lib.scs_amd_linsys_get_stats.restype = None
         lib.scs_amd_linsys_get_stats.argtypes = [C.c_void_p, C.POINTER(T.ScsAmdStats)]

@@ -10,6 +10,23 @@ typedef scs_float real;
 
 struct BigPsd; // psd_big.h
 
+// block projections (cones_multi.h): state and staging at one width, per column position; nothing of it is shared with the
+// single-vector path
+struct ConeMulti {
+  ~ConeMulti();
+  int width = 0;
+  DevBuf<real> s;              // m x W: the saved input of the Moreau wrapper
+  DevBuf<real> cols;           // W columns of length m, column major: what the single-vector device code of the box and PSD cones works on
+  DevBuf<real> xblk;           // m x W: the block of the host-pointer entry (allocated by it)
+  DevBuf<real> tile_part;      // per (tile, column)
+  DevBuf<real> big_coef;       // per (big cone, column): [head, tail multiplier]
+  DevBuf<real> box_t;          // W Newton warm starts
+  DevBuf<int> psd_off, psd_k;  // tables of the LDS kernel, replicated per column
+  DevBuf<real> psd_vprev, psd_tscratch; // per (column, block)
+  std::vector<BigPsd *> big;   // per column: blocks beyond the LDS path
+  long long psd_calls = 0;     // block projections since the last cold start
+};
+
 struct ConeDev {
   ~ConeDev();
   ConeDev() = default;
@@ -34,7 +51,7 @@ struct ConeDev {
   DevBuf<real> tile_part;   // per-tile sum of squares of the tail
   DevBuf<real> big_coef;    // per big cone: [head, tail multiplier]
   // PSD cones
-  int n_psd = 0, psd_kmax = 0, psd_lds_kmax = 0;
+  int n_psd = 0, psd_kmax = 0, psd_lds_kmax = 0, psd_row0 = 0; // psd_row0: first row of the PSD blocks (they end at exp_off)
   DevBuf<int> psd_off, psd_k;
   BigPsd *psd_big = nullptr; // blocks of order > PSD_LDS_KMAX: chip-wide Jacobi steps
   DevBuf<real> psd_vprev;   // per block: eigenbasis of the previous projection (warm start of the LDS kernel, every order it handles)
@@ -59,6 +76,13 @@ struct ConeDev {
   // x (device, length m) <- Proj_{K*}^{R}(x) via Moreau; `scratch` is a length-m
   // device buffer that receives the saved input.
   void proj_dual(real *x, real *scratch, const real *r_y);
+  // the same for a block of K vectors in the m x W block layout (cones_multi.h), in place; columns K .. W - 1 become zero
+  ConeMulti *multi = nullptr;
+  void ensure_multi(int W);
+  void proj_dual_multi(real *X, int W, int K, const real *r_y);
+  // launches shared by the two paths
+  void launch_box(real *tx, real *t_warm, const real *rb);
+  void launch_psd_lds(real *cw, int nblocks, const int *off, const int *kk, real *tscratch, real *vprev, int warm);
   int rows() const { return m; }
 };
 

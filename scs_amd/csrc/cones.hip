@@ -902,7 +902,10 @@ __global__ __launch_bounds__(PSD_THREADS) void k_psd_jacobi(real *x, const int *
 #include "psd_big.h"
 namespace scsamd {
 
-ConeDev::~ConeDev() { delete psd_big; }
+ConeDev::~ConeDev() {
+  delete psd_big;
+  delete multi;
+}
 void ConeDev::reset_warm_start() {
   psd_calls = 0;
   if (psd_big) psd_big->reset_warm_start();
@@ -1057,6 +1060,7 @@ void ConeDev::init(const ScsCone *k, int m_, const real *D, hipStream_t s) {
   // PSD
   std::vector<int> poff, pk;
   psd_kmax = 0;
+  psd_row0 = off;
   for (int i = 0; i < k->ssize; ++i) {
     poff.push_back(off);
     pk.push_back(k->s[i]);
@@ -1084,6 +1088,8 @@ void ConeDev::init(const ScsCone *k, int m_, const real *D, hipStream_t s) {
     psd_big->init(pk, PSD_LDS_KMAX, stream);
   }
   psd_calls = 0;
+  delete multi; // block state is sized by the cone: built again at the next block call
+  multi = nullptr;
   psd_pipe = 1;
   if (const char *e = opt_get("psd_pipe")) psd_pipe = std::max(0, std::min(2, atoi(e)));
   // warm start of the LDS kernel: sized and gated by the largest block that kernel handles (blocks beyond the LDS path
@@ -1110,22 +1116,43 @@ void ConeDev::init(const ScsCone *k, int m_, const real *D, hipStream_t s) {
   if (off != m) throw HipError("scs_amd: cone rows do not add up to m");
 }
 
+// tx: the box cone's rows [t; x] of one vector; t_warm: its Newton start, read and updated
+void ConeDev::launch_box(real *tx, real *t_warm, const real *rb) {
+  if (box_multi) {
+    const int g = std::max(1, std::min(BOX_MULTI_GRID, (bsize - 1 + 8 * SCSAMD_BLOCK - 1) / (8 * SCSAMD_BLOCK)));
+    BoxCtl *ctl = reinterpret_cast<BoxCtl *>(box_ctl.p);
+    for (int it = 0; it <= BOX_MAX_ITERS; ++it)
+      hipLaunchKernelGGL(k_box_step, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, tx, bl.p, bu.p, bsize, t_warm, rb, ctl, box_part.p, it);
+    hipLaunchKernelGGL(k_box_apply, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, tx, bl.p, bu.p, bsize, t_warm, ctl);
+  } else {
+    hipLaunchKernelGGL(k_box, dim3(1), dim3(BOX_THREADS), 0, stream, tx, bl.p, bu.p, bsize, t_warm, rb);
+  }
+}
+
+// one launch of k_psd_jacobi over `nblocks` blocks described by (off, kk): the blocks of order <= PSD_LDS_KMAX among them
+void ConeDev::launch_psd_lds(real *cw, int nblocks, const int *off, const int *kk, real *tscratch, real *vprev, int warm) {
+  const int lds_kmax = std::min(psd_kmax, psd_lds_kmax); // largest block order held in LDS
+  const int K2l = (lds_kmax + 1) & ~1;
+  const bool carry = vprev != nullptr;
+  // round 5: pipelined step (second copy of A in LDS) whenever three matrices fit; SCS_AMD_PSD_PIPE=0 keeps the two-phase step (A/B)
+  const int pipe = K2l <= PSD_WARM_KMAX ? psd_pipe : 0; // psd_pipe: option read in init (0 two-phase, 1 look-ahead, 2 signal form)
+  const size_t lds = PSD_LDS_HEADER + (size_t)((pipe || (carry && !tscratch)) ? 3 : 2) * K2l * (K2l | 1) * sizeof(real);
+  auto launch = [&](auto kern) {
+    if (lds > 48 * 1024)
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(PSD_THREADS), lds, stream, cw, off, kk, tscratch, lds_kmax, lds_kmax, status.p, vprev, warm);
+  };
+  if (pipe == 2) launch(k_psd_jacobi<2>);
+  else if (pipe == 1) launch(k_psd_jacobi<1>);
+  else launch(k_psd_jacobi<0>);
+}
+
 void ConeDev::proj_primal(real *cw, const real *r_y) {
   if (z + l > 0)
     hipLaunchKernelGGL(k_zero_pos, dim3(small_grid(z + l)), dim3(SCSAMD_BLOCK), 0, stream, cw, z, l);
   if (bsize > 0) {
     const real *rb = r_y ? r_y + box_off : (const real *)nullptr;
-    if (box_multi) {
-      const int g = std::max(1, std::min(BOX_MULTI_GRID, (bsize - 1 + 8 * SCSAMD_BLOCK - 1) / (8 * SCSAMD_BLOCK)));
-      BoxCtl *ctl = reinterpret_cast<BoxCtl *>(box_ctl.p);
-      for (int it = 0; it <= BOX_MAX_ITERS; ++it)
-        hipLaunchKernelGGL(k_box_step, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, cw + box_off, bl.p, bu.p, bsize, box_t.p,
-                           rb, ctl, box_part.p, it);
-      hipLaunchKernelGGL(k_box_apply, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, cw + box_off, bl.p, bu.p, bsize, box_t.p,
-                         ctl);
-    } else {
-      hipLaunchKernelGGL(k_box, dim3(1), dim3(BOX_THREADS), 0, stream, cw + box_off, bl.p, bu.p, bsize, box_t.p, rb);
-    }
+    launch_box(cw + box_off, box_t.p, rb);
   }
   if (n_tiny)
     hipLaunchKernelGGL(k_soc_tiny, dim3(small_grid(n_tiny)), dim3(SCSAMD_BLOCK), 0, stream, cw, tiny_off.p,
@@ -1140,23 +1167,9 @@ void ConeDev::proj_primal(real *cw, const real *r_y) {
                        tile_cone.p, big_off.p, big_coef.p, n_tiles);
   }
   if (n_psd) {
-    const int lds_kmax = std::min(psd_kmax, psd_lds_kmax); // largest block order held in LDS
-    const int K2l = (lds_kmax + 1) & ~1;
-    const bool carry = psd_vprev.p != nullptr;
-    // round 5: pipelined step (second copy of A in LDS) whenever three matrices fit; SCS_AMD_PSD_PIPE=0 keeps the two-phase step (A/B)
-    const int pipe = K2l <= PSD_WARM_KMAX ? psd_pipe : 0; // psd_pipe: option read in init (0 two-phase, 1 look-ahead, 2 signal form)
-    const size_t lds = PSD_LDS_HEADER + (size_t)((pipe || (carry && !psd_tscratch.p)) ? 3 : 2) * K2l * (K2l | 1) * sizeof(real);
-    const int warm = carry && (psd_calls % PSD_WARM_RESET) != 0;
+    const int warm = psd_vprev.p != nullptr && (psd_calls % PSD_WARM_RESET) != 0;
     ++psd_calls;
-    auto launch = [&](auto kern) {
-      if (lds > 48 * 1024)
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kern, dim3(n_psd), dim3(PSD_THREADS), lds, stream, cw, psd_off.p, psd_k.p, psd_tscratch.p, lds_kmax, lds_kmax,
-                         status.p, psd_vprev.p, warm);
-    };
-    if (pipe == 2) launch(k_psd_jacobi<2>);
-    else if (pipe == 1) launch(k_psd_jacobi<1>);
-    else launch(k_psd_jacobi<0>);
+    launch_psd_lds(cw, n_psd, psd_off.p, psd_k.p, psd_tscratch.p, psd_vprev.p, warm);
     if (psd_big) psd_big->project(cw, psd_off.p, psd_k.p, status.p, stream);
   }
   proj_exp_pow(cw);
@@ -1185,6 +1198,7 @@ void ConeDev::proj_dual(real *x, real *scratch, const real *r_y) {
 }
 
 } // namespace scsamd
+#include "cones_multi.h" // blocks of vectors: K projections at once
 
 // ============================================================================
 // B1': host-pointer cone projection (replaces _scs_init_cone / _scs_proj_dual_cone /
@@ -1236,6 +1250,80 @@ scs_int scs_amd_cone_proj_dual(ScsAmdConeWork *c, scs_float *x, const scs_float 
     return -1;
   }
   return 0;
+}
+
+// ---- blocks of vectors: K projections of scs_amd_cone_proj_dual (cones.c:1552-1596) on one workspace ----
+scs_int scs_amd_cone_multi_width(scs_int nrhs) { return (scs_int)cone_multi_width((long long)nrhs); }
+
+scs_int scs_amd_cone_proj_dual_multi(ScsAmdConeWork *c, scs_int nrhs, scs_float *X, scs_int ldx, const scs_float *r_y) {
+  if (!c || !X || nrhs < 1) return -1;
+  ConeDev &cd = c->cd;
+  const size_t m = cd.m, sz = sizeof(real);
+  if ((long long)ldx < (long long)m) return -1;
+  scs_int ret = 0;
+  try {
+    for (scs_int c0 = 0; c0 < nrhs; c0 += CONE_W_MAX) { // chunks of at most 16 columns
+      const int K = (int)std::min<scs_int>(CONE_W_MAX, nrhs - c0);
+      scs_float *Xc = X + (size_t)c0 * (size_t)ldx;
+      if (nrhs == 1) { // a block of one column IS the single-vector path, bit for bit
+        const scs_int r = scs_amd_cone_proj_dual(c, Xc, r_y);
+        if (r < 0) return r;
+        if (r > 0) ret = r;
+        continue;
+      }
+      const int W = std::max(2, cone_multi_width(K)); // a remainder of one column (17, 33, ... columns) is a block of width 2: block state only
+      cd.ensure_multi(W);
+      ConeMulti &mc = *cd.multi;
+      if (!mc.xblk.p) mc.xblk.alloc(m * W ? m * W : 1);
+      const int g = std::max(1, std::min(2048, ceil_div((long long)m, SCSAMD_BLOCK)));
+      if (m) HIP_CHECK(hipMemcpy2DAsync(mc.cols.p, m * sz, Xc, (size_t)ldx * sz, m * sz, (size_t)K, hipMemcpyHostToDevice, c->stream));
+      if (r_y) cd.r_stage.upload(r_y, m, c->stream);
+      CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cone_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, c->stream, mc.cols.p, mc.xblk.p, (int)m, K));
+      cd.proj_dual_multi(mc.xblk.p, W, K, r_y ? cd.r_stage.p : nullptr);
+      CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cone_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, c->stream, mc.cols.p, mc.xblk.p, (int)m, K));
+      if (m) HIP_CHECK(hipMemcpy2DAsync(Xc, (size_t)ldx * sz, mc.cols.p, m * sz, m * sz, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+      const int bad = cd.take_status(c->stream); // synchronises the stream
+      HIP_CHECK(hipGetLastError());
+      if (bad > 0) ret = 1; // PSD blocks that hit the sweep cap, over all columns: positive, not fatal (as scs_amd_cone_proj_dual)
+    }
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(c->stream); // nothing of this call may still be reading or writing the caller's block
+    return -1;
+  }
+  return ret;
+}
+
+// the same on device pointers, in place, on the workspace's private stream: the caller synchronises its own work before the call and
+// calls scs_amd_cone_sync before it reads the result (the contract of scs_amd_linsys_*_dev)
+scs_int scs_amd_cone_proj_dual_dev(ScsAmdConeWork *c, scs_float *x_dev, const scs_float *r_y_dev) {
+  if (!c || !x_dev) return -1;
+  try {
+    c->cd.proj_dual(x_dev, c->cd.s_stage.p, r_y_dev);
+    HIP_CHECK(hipGetLastError());
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
+}
+scs_int scs_amd_cone_proj_dual_multi_dev(ScsAmdConeWork *c, scs_int nrhs, scs_float *X_dev, const scs_float *r_y_dev) {
+  if (!c || !X_dev) return -1;
+  const int W = cone_multi_width((long long)nrhs);
+  if (W == 0) return -1;
+  if (W == 1) return scs_amd_cone_proj_dual_dev(c, X_dev, r_y_dev);
+  try {
+    c->cd.proj_dual_multi(X_dev, W, (int)nrhs, r_y_dev);
+    HIP_CHECK(hipGetLastError());
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
+}
+scs_int scs_amd_cone_sync(ScsAmdConeWork *c) {
+  if (!c) return -1;
+  return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : -1;
 }
 
 void scs_amd_cone_finish(ScsAmdConeWork *c) { delete c; }
