@@ -289,6 +289,14 @@ typedef struct {
 } ScsAmdStats;
 
 void scs_amd_linsys_get_stats(const ScsLinSysWork *w, ScsAmdStats *out);
+/* How the host fed the PCG loop of this workspace since it was created (option cg_pace):
+ *   out[0]  CG iterations enqueued, counted in iterations: a quantum is one iteration (its launches) or one replayed graph of 8
+ *   out[1]  CG iterations the device executed (ScsAmdStats.cg_iters); out[0] - out[1] was enqueued past convergence
+ *   out[2]  blocking synchronisations inside the linear solves (0 with cg_pace=1 unless `debug` / `trace_file` ask for more)
+ *   out[3]  linear solves
+ * Plain host counters: no device call, no synchronisation.  Block solves (scs_amd_solve_lin_sys_multi) count in out[1] and out[3] only. */
+void scs_amd_linsys_get_cg_pacing(const ScsLinSysWork *w, long long out[4]);
+void scs_amd_get_cg_pacing(const ScsWork *w, long long out[4]);
 void scs_amd_linsys_set_profiling(ScsLinSysWork *w, scs_int on);
 /* Pieces of the operator of linsys/cpu/indirect/private.c:106-119 (`mat_vec`) on DEVICE pointers, for a caller that splits
  * ONE linear system by rows of A across GPUs (scs_amd/shard.py): the workspace is created by

@@ -152,6 +152,8 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
         lib.scs_amd_linsys_get_stats.argtypes = [C.c_void_p, C.POINTER(T.ScsAmdStats)]
         lib.scs_amd_linsys_set_profiling.restype = None
         lib.scs_amd_linsys_set_profiling.argtypes = [C.c_void_p, scs_int]
+        lib.scs_amd_linsys_get_cg_pacing.restype = None
+        lib.scs_amd_linsys_get_cg_pacing.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
         for nm in ("scs_amd_linsys_mat_vec_dev", "scs_amd_linsys_mul_a_dev", "scs_amd_linsys_mul_at_dev"):
             fn = getattr(lib, nm)
             fn.restype = scs_int
@@ -189,6 +191,8 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_get_stats.argtypes = [C.c_void_p, C.POINTER(T.ScsAmdStats)]
             lib.scs_amd_set_profiling.restype = None
             lib.scs_amd_set_profiling.argtypes = [C.c_void_p, scs_int]
+            lib.scs_amd_get_cg_pacing.restype = None
+            lib.scs_amd_get_cg_pacing.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
             lib.scs_amd_solve_begin.restype = scs_int
             lib.scs_amd_solve_begin.argtypes = [C.c_void_p, C.POINTER(T.ScsSolution), scs_int]
             lib.scs_amd_solve_steps.restype = scs_int

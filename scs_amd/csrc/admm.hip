@@ -1626,6 +1626,11 @@ void scs_amd_set_profiling(ScsWork *w, scs_int on) {
   w->ls.profiling = on != 0;
 }
 
+void scs_amd_get_cg_pacing(const ScsWork *w, long long out[4]) {
+  if (!w || !out) return;
+  w->ls.get_cg_pacing(out);
+}
+
 void scs_amd_get_stats(const ScsWork *cw, ScsAmdStats *out) {
   if (!cw || !out) return;
   ScsWork *w = const_cast<ScsWork *>(cw);

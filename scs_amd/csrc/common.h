@@ -145,10 +145,10 @@ template <typename T> struct PinnedBuf {
   ~PinnedBuf() {
     if (p) (void)hipHostFree(p);
   }
-  void alloc(size_t count) {
+  void alloc(size_t count, unsigned flags = hipHostMallocDefault) {
     if (p) (void)hipHostFree(p);
     n = count;
-    HIP_CHECK(hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault));
+    HIP_CHECK(hipHostMalloc((void **)&p, count * sizeof(T), flags));
     memset(p, 0, count * sizeof(T));
   }
 };

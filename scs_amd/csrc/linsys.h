@@ -13,7 +13,7 @@ namespace scsamd {
 int selected_device(); // device chosen by scs_amd_set_device (HIP's current device is per host thread)
 
 // Control block of one PCG solve, lives in device memory; the host reads it back
-// once per enqueued batch of iterations.
+// once per enqueued batch of iterations (cg_pace=0) or not at all (cg_pace=1: the progress word below).
 struct CgCtl {
   real ztr[2];   // z'r, double-buffered by iteration parity
   real norm_r;   // ||r||_inf after the last completed iteration
@@ -23,7 +23,17 @@ struct CgCtl {
   int cg_done;   // converged (or breakdown): remaining iteration kernels return
   int iters;     // PCG iterations performed (reference counting, private.c:203,216)
   int max_its;   // 10 n (private.c:307): the device stops there even if more iterations were enqueued
+  unsigned seq;  // sequence number of this solve (k_rhs_prep): tags every progress word the solve publishes
 };
+
+// Progress word of a paced solve: ONE aligned 64-bit word in pinned, host-coherent, device-mapped memory that the lane which
+// writes CgCtl::iters / cg_done also stores, so the host learns "stopped, after how many iterations" from one load without
+// stopping the stream.  bits 63..32: sequence number of the solve (a word left by the previous solve never matches);
+// bits 31..1: iterations done (max_its < 2^31); bit 0: done.
+typedef unsigned long long cg_word;
+__host__ __device__ inline cg_word cg_word_pack(unsigned seq, int iters, int done) {
+  return ((cg_word)seq << 32) | ((cg_word)(unsigned)iters << 1) | (cg_word)(done ? 1 : 0);
+}
 
 // Control block of a block solve (linsys_multi.h): what CgCtl holds, per column, plus one word that says every column has stopped.
 struct CgCtlM {
@@ -91,6 +101,21 @@ struct LinSys {
   DevBuf<real> partC, partD;         // use_cg3: partials of z'Gp and Gp'MGp
   DevBuf<CgCtl> ctl;
   PinnedBuf<CgCtl> hctl;
+  // paced enqueue (cg_pace): the progress word, the sequence number of the last solve, how many quanta the
+  // host may run ahead of the published iteration count, and what scs_amd_get_cg_pacing reports
+  PinnedBuf<cg_word> prog;
+  cg_word *prog_dev = nullptr; // device view of `prog`; null = nothing is published (cg_pace=0, row-sharded workspaces)
+  unsigned cg_seq = 0;
+  bool cg_pace = true;
+  int cg_lead = 4;
+  long long n_enq_its = 0, n_syncs = 0; // CG iterations enqueued (a graph counts CG_GRAPH_ITERS); blocking waits inside solve_dev
+  cg_word progress_word() const;
+  bool wait_word(cg_word seen, double iter_us);
+  // options read once in init (options.h: "read when a workspace is created")
+  bool opt_debug = false;
+  const char *opt_trace_file = nullptr; // interned by options.h: stays valid
+  int vec_cap = 0;                      // cap on the grid of the vector kernels (vec_max_grid)
+  int vec_grid(long long len) const;
 
   // staging for the host-pointer boundary (B1)
   DevBuf<real> b_stage, s_stage, dr_stage;
@@ -144,6 +169,7 @@ struct LinSys {
   void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
   long long matvec_bytes() const { return A.algorithmic_bytes() + At.algorithmic_bytes(); }
   void harvest_timers();
+  void get_cg_pacing(long long out[4]) const; // scs_amd_get_cg_pacing (include/scs_amd.h)
 
 private:
   void build_preconditioner();

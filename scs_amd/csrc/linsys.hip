@@ -11,10 +11,12 @@
 //   K2 csr_stream<GP>    Gp = R_x p + P p + A' tmp,  partials of p'Gp
 //   K3 cg_update         alpha; x += alpha p; r -= alpha Gp; z = M r; partials z'r, |r|_inf
 //   K4 cg_direction      convergence test; beta; p = z + beta p
-// with all scalars (alpha, beta, z'r, ||r||, tol, done) living in HBM.  The host
-// enqueues iterations in batches sized from the previous solve's count and reads
-// one control block per batch; kernels issued past convergence return at once,
-// so the iterate returned is exactly the first one meeting the tolerance.
+// with all scalars (alpha, beta, z'r, ||r||, tol, done) living in HBM.  Kernels issued
+// past convergence return at once, so the iterate returned is exactly the first one
+// meeting the tolerance.  The host keeps the queue a few iterations ahead of the
+// iteration count the device publishes in a host-visible word (cg_pace, solve_dev),
+// or -- cg_pace=0, row-sharded workspaces -- enqueues batches sized from the previous
+// solve's count and reads one control block per batch.
 #include "linsys.h"
 #include <thread>
 #include <exception>
@@ -24,11 +26,14 @@
 #include "host_transpose.h"
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 
 namespace scsamd {
 
 constexpr int CG_GRAPH_ITERS = 8;               // iterations per captured graph (even: slot parity q = iteration & 1)
 constexpr long long CG_GRAPH_MAX_NNZ = 2000000; // systems up to this many nonzeros replay the CG loop from a graph
+constexpr int CG_LEAD_DEFAULT = 4;              // quanta the paced enqueue loop runs ahead of the device (cg_lead; profiles/cg_pacing.md)
+constexpr int CG_PACE_SPIN = 64;                // empty polls (each followed by a yield) before the waiting host thread starts to sleep
 
 
 constexpr int VEC_MAX_GRID = 512; // every consumer workgroup re-reduces the producers' partials: 2048 WGs cost K4 64 MB of L2 reads (measured 2.5 % of a CG iteration)
@@ -37,17 +42,20 @@ static_assert(PART_CAP >= SPMV_MAX_GRID && PART_CAP >= WR_MAX_GRID && PART_CAP >
 
 CsrDev::~CsrDev() { delete wave; }
 
-static inline int vec_grid(long long len) {
-  // read once per process (called per launch: no table lookups here); tests that shrink it run in their own process
-  static const int cap = [] {
-    const char *e = opt_get("vec_max_grid"); // tests shrink it to force grid-striding
-    int g = e ? atoi(e) : VEC_MAX_GRID;
-    return (g >= 1 && g <= PART_CAP / 2) ? g : VEC_MAX_GRID; // z'r and |r| partials share one PART_CAP array (measurement sweeps go to 2048)
-  }();
+// grid of a vector kernel over `len` entries; the cap (vec_max_grid: tests shrink it to force grid-striding) is read in init
+int LinSys::vec_grid(long long len) const {
+  const int cap = vec_cap > 0 ? vec_cap : VEC_MAX_GRID;
   long long g = (len + SCSAMD_BLOCK - 1) / SCSAMD_BLOCK;
   if (g < 1) g = 1;
   if (g > cap) g = cap;
   return (int)g;
+}
+
+// The lane that writes CgCtl::iters / cg_done tells the host as well (linsys.h, cg_word).  System scope: the word lives in host
+// memory.  Release as a matter of form -- the host acts on the word alone (sequence number, count and flag travel in one store)
+// and reads everything else behind the stream's own ordering.
+__device__ __forceinline__ void publish_progress(cg_word *w, unsigned seq, int iters, int done) {
+  if (w) __hip_atomic_store(w, cg_word_pack(seq, iters, done), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ----------------------------------------------------------------------------
@@ -72,7 +80,8 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_rhs_prep(real *b, const real *
                                                            real *tmp, int n, int m,
                                                            const real *part, int pcount, CgCtl *ctl,
                                                            real tol, const real *warm_part,
-                                                           int warm_cnt, real warm_scale, int max_its) {
+                                                           int warm_cnt, real warm_scale, int max_its, unsigned seq,
+                                                           cg_word *prog) {
   __shared__ real red[4];
   const real nb = reduce_partials_max(part, pcount, red);
   const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gs = gridDim.x * blockDim.x;
@@ -99,6 +108,8 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_rhs_prep(real *b, const real *
     ctl->norm_r = 0;
     ctl->ztr[0] = 0;
     ctl->ztr[1] = 0;
+    ctl->seq = seq;
+    publish_progress(prog, seq, 0, zero ? 1 : 0); // a zero right-hand side is done here; otherwise the word now belongs to this solve
   }
 }
 
@@ -137,7 +148,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg_init(real *x, const real *_
 // private.c:163 early-out with max(tol, 1e-12); p = z
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg_start(real *p, const real *__restrict__ z, int n,
                                                            const real *part_ztr, const real *part_max,
-                                                           int pcount, CgCtl *ctl) {
+                                                           int pcount, CgCtl *ctl, cg_word *prog) {
   __shared__ real red[4];
   if (ctl->zero_rhs) return;
   const real ztr = reduce_partials_sum(part_ztr, pcount, red);
@@ -150,7 +161,10 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg_start(real *p, const real *
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ctl->ztr[0] = ztr;
     ctl->norm_r = nr;
-    if (conv) ctl->cg_done = 1;
+    if (conv) {
+      ctl->cg_done = 1;
+      publish_progress(prog, ctl->seq, 0, 1);
+    }
   }
 }
 
@@ -285,7 +299,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg_update(real *x, real *r, re
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg_direction(real *p, const real *__restrict__ z, int n,
                                                                const real *part_ztr,
                                                                const real *part_max, int pcount,
-                                                               CgCtl *ctl, int parity, int dmode) {
+                                                               CgCtl *ctl, int parity, int dmode, cg_word *prog) {
   __shared__ real red[4];
   // as in k_cg_update: everything this kernel reads is requested up front (one round trip, not four)
   const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gs = gridDim.x * blockDim.x;
@@ -343,8 +357,11 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg_direction(real *p, const re
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ctl->ztr[parity ^ 1] = ztr;
     ctl->norm_r = nr;
-    if (!brk) ctl->iters += 1; // converged at i -> i+1 ; breakdown returns i (private.c:203,216)
-    if (conv || brk || ctl->iters >= ctl->max_its) ctl->cg_done = 1;
+    const int its = ctl->iters + (brk ? 0 : 1); // converged at i -> i+1 ; breakdown returns i (private.c:203,216)
+    const bool stop = conv || brk || its >= ctl->max_its;
+    ctl->iters = its;
+    if (stop) ctl->cg_done = 1;
+    publish_progress(prog, ctl->seq, its, stop ? 1 : 0);
   }
 }
 
@@ -366,7 +383,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg3_update(real *x, real *r, r
                                                              const real *__restrict__ M, int n, const real *part_pgp,
                                                              const real *part_d1, const real *part_d2, int cnt_sp,
                                                              const real *part_ztr_prev, const real *part_max_prev, int cnt_v,
-                                                             real *part_ztr, real *part_max, CgCtl *ctl, int it) {
+                                                             real *part_ztr, real *part_max, CgCtl *ctl, int it, cg_word *prog) {
   __shared__ real red[4];
   const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gs = gridDim.x * blockDim.x;
   const int nv = n / RVW;
@@ -412,6 +429,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg3_update(real *x, real *r, r
       ctl->iters = it; // converged after `it` iterations -> it; breakdown in iteration `it` -> it (private.c:203,216)
     }
     if (stop) ctl->cg_done = 1;
+    publish_progress(prog, ctl->seq, it, stop ? 1 : 0); // `it` iterations are complete, whether or not this launch goes on
   }
   if (stop) return;
   const real alpha = ztr / pgp;
@@ -535,7 +553,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg2_a(CsrView A, const real *_
                                                        const real *__restrict__ r_old, real *r_new,
                                                        const real *__restrict__ Gp, const real *__restrict__ M,
                                                        const real *__restrict__ p_old, real *p_new_g, int n,
-                                                       const real *part_pgp, int cnt_pgp, int gv, CgCtl *ctl, int parity) {
+                                                       const real *part_pgp, int cnt_pgp, int gv, CgCtl *ctl, int parity, cg_word *prog) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cg2_smem[];
   real *pl = reinterpret_cast<real *>(cg2_smem); // n entries: z, then the new p
   __shared__ real prod[NNZ_PER_BLOCK];
@@ -679,8 +697,11 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_cg2_a(CsrView A, const real *_
   if (writer && tid == 0) {
     ctl->ztr[parity ^ 1] = ztr;
     ctl->norm_r = nr;
-    if (!brk) ctl->iters += 1;
-    if (conv || brk || ctl->iters >= ctl->max_its) ctl->cg_done = 1;
+    const int its = ctl->iters + (brk ? 0 : 1);
+    const bool stop = conv || brk || its >= ctl->max_its;
+    ctl->iters = its;
+    if (stop) ctl->cg_done = 1;
+    publish_progress(prog, ctl->seq, its, stop ? 1 : 0);
   }
   if (conv || brk) return;
   __syncthreads();
@@ -725,7 +746,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_linsys_fused(CsrView A, CsrVi
                                                                 real *b, const real *s, const real *rx,
                                                                 const real *ry, const real *M, real *p, real *r,
                                                                 real *Gp, real *z, real *tmp, CgCtl *ctl, real tol,
-                                                                int form_tol, real tol_scale, long long max_its) {
+                                                                int form_tol, real tol_scale, long long max_its, unsigned seq,
+                                                                cg_word *prog) {
   __shared__ real red[FUSED_THREADS / SCSAMD_WAVE];
   const int tid = threadIdx.x, n = At.rows, m = A.rows;
   const CsrView *Pp = has_P ? &P : nullptr;
@@ -752,6 +774,8 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_linsys_fused(CsrView A, CsrVi
     for (int i = tid; i < n + m; i += FUSED_THREADS) b[i] = 0;
     if (tid == 0) {
       ctl->zero_rhs = 1; ctl->cg_done = 1; ctl->iters = 0; ctl->tol = t; ctl->rhs_norm = nb; ctl->norm_r = 0;
+      ctl->seq = seq;
+      publish_progress(prog, seq, 0, 1);
     }
     return;
   }
@@ -830,7 +854,12 @@ __global__ __launch_bounds__(FUSED_THREADS) void k_linsys_fused(CsrView A, CsrVi
   if (tid == 0) {
     ctl->zero_rhs = 0; ctl->cg_done = 1; ctl->iters = iters; ctl->tol = t; ctl->rhs_norm = nb; ctl->norm_r = nr;
     ctl->ztr[0] = ztr; ctl->ztr[1] = 0;
+    ctl->seq = seq;
   }
+  // the loop runs on the device: the host waits for this one word instead of a read-back (after the barrier: the solution, which
+  // the host reads behind the stream anyway, is complete when the word says so)
+  __syncthreads();
+  if (tid == 0) publish_progress(prog, seq, iters, 1);
 }
 
 // ----------------------------------------------------------------------------
@@ -936,7 +965,15 @@ void LinSys::init(const CscView *A_csc, const CscView *P_csc, hipStream_t s, Csr
     HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     own_stream = true;
   }
-  const bool dbg_t = opt_get("debug") != nullptr;
+  // the options of the solve path are read here, once (options.h: "read when a workspace is created, never during a solve")
+  opt_debug = opt_get("debug") != nullptr;
+  opt_trace_file = opt_get("trace_file");
+  vec_cap = VEC_MAX_GRID;
+  if (const char *e = opt_get("vec_max_grid")) { // tests shrink it to force grid-striding
+    const int g = atoi(e);
+    if (g >= 1 && g <= PART_CAP / 2) vec_cap = g; // z'r and |r| partials share one PART_CAP array (measurement sweeps go to 2048)
+  }
+  const bool dbg_t = opt_debug;
   auto t_now = [] {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -1109,6 +1146,14 @@ void LinSys::init(const CscView *A_csc, const CscView *P_csc, hipStream_t s, Csr
   }
   ctl.alloc(1);
   hctl.alloc(1);
+  // the progress word of the paced solves: pinned, host-coherent, device-mapped (linsys.h, cg_word)
+  cg_pace = true;
+  if (const char *e = opt_get("cg_pace")) cg_pace = atoi(e) != 0;
+  cg_lead = CG_LEAD_DEFAULT;
+  if (const char *e = opt_get("cg_lead")) cg_lead = std::max(1, std::min(atoi(e), 1024));
+  prog.alloc(1, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable);
+  prog_dev = nullptr;
+  if (cg_pace) HIP_CHECK(hipHostGetDevicePointer((void **)&prog_dev, prog.p, 0));
   HIP_CHECK(hipStreamSynchronize(stream));
 }
 
@@ -1130,6 +1175,9 @@ void LinSys::set_shard(ShardHook *h) {
     use_cg2 = false;
     use_cg3 = false;
     use_graph = false;
+    // shard_allreduce sits inside the iteration and every rank must enqueue the same sequence: batches, as before
+    cg_pace = false;
+    prog_dev = nullptr;
   }
 }
 
@@ -1184,6 +1232,13 @@ void LinSys::mul_P(const real *x_n, real *y_n) {
   launch_spmv(EPI_PLAIN, P, x_n, y_n, e, nullptr);
 }
 
+void LinSys::get_cg_pacing(long long out[4]) const {
+  out[0] = n_enq_its;
+  out[1] = tot_cg_its;
+  out[2] = n_syncs;
+  out[3] = n_solves;
+}
+
 void LinSys::harvest_timers() {
   spmv_timer.harvest();
   cg_timer.harvest();
@@ -1209,7 +1264,7 @@ void LinSys::enqueue_cg2_iteration(long long it) {
   } else {
     const int q = (int)((it - 1) & 1);
     hipLaunchKernelGGL(k_cg2_a, dim3(A.grid()), dim3(SCSAMD_BLOCK), (size_t)n * sizeof(real), stream, A.view(), ry.p, tmp.p, cg_x,
-                       rbuf[(it - 1) & 1], rbuf[it & 1], Gp.p, M.p, pbuf[(it - 1) & 1], p_cur, n, partA.p, gAt, gv, c, q);
+                       rbuf[(it - 1) & 1], rbuf[it & 1], Gp.p, M.p, pbuf[(it - 1) & 1], p_cur, n, partA.p, gAt, gv, c, q, prog_dev);
     n_spmv++;
   }
   EpiArgs e2{rx.p, p_cur, nullptr, partA.p};
@@ -1239,7 +1294,7 @@ void LinSys::enqueue_cg_iteration(int q) {
   hipLaunchKernelGGL(k_cg_update, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, cg_x, r.p, z.p, p.p, Gp.p, M.p, n,
                      part_pgp, cnt_pgp, part_ztr, part_max, c, q, nt_mode);
   hipLaunchKernelGGL(k_cg_direction, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, p.p, z.p, n, part_ztr, part_max,
-                     gv, c, q, dir_mode);
+                     gv, c, q, dir_mode, prog_dev);
 }
 
 // three-kernel iteration (k_cg3_update): K1, [P p], K2 with the three dot products in its epilogue, the fused vector kernel
@@ -1263,7 +1318,7 @@ void LinSys::enqueue_cg3_iteration(long long it) {
   e2.partial3 = partD.p;
   launch_spmv(EPI_GP3, At, tmp.p, Gp.p, e2, &c->cg_done);
   hipLaunchKernelGGL(k_cg3_update, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, cg_x, r.p, p.p, Gp.p, M.p, n, partA.p, partC.p, partD.p, gAt,
-                     ztr_prev, max_prev, gv, ztr_cur, max_cur, c, (int)std::min<long long>(it, 2147483647LL));
+                     ztr_prev, max_prev, gv, ztr_cur, max_cur, c, (int)std::min<long long>(it, 2147483647LL), prog_dev);
 }
 
 // Capture CG_GRAPH_ITERS iterations into an executable graph.  Any failure leaves cg_graph null
@@ -1296,11 +1351,36 @@ bool LinSys::build_cg_graph() {
   return ok;
 }
 
+cg_word LinSys::progress_word() const { return __atomic_load_n(prog.p, __ATOMIC_ACQUIRE); }
+
+// Wait until the progress word differs from `seen` (true), or until the stream has nothing left to run (false; the caller reads the
+// word once more: what an idle stream has published is in host memory).  Never a busy spin: see the policy at the paced loop.
+bool LinSys::wait_word(cg_word seen, double iter_us) {
+  using clk = std::chrono::steady_clock;
+  clk::time_point t_query = clk::now();
+  const double nap_us = iter_us > 0 ? std::min(std::max(0.5 * iter_us, 2.0), 250.0) : 20.0;
+  for (int empty = 0;; ++empty) {
+    if (progress_word() != seen) return true;
+    if (empty < CG_PACE_SPIN) std::this_thread::yield();
+    else std::this_thread::sleep_for(std::chrono::nanoseconds((long long)(nap_us * 1e3)));
+    const clk::time_point now = clk::now();
+    if (now - t_query >= std::chrono::milliseconds(1)) { // a faulted stream must not leave the host polling for ever
+      t_query = now;
+      HIP_CHECK(hipGetLastError()); // (a pending launch error would be wiped with the query's "not ready" below)
+      const hipError_t e = hipStreamQuery(stream);
+      if (e == hipSuccess) return false;
+      if (e != hipErrorNotReady) HIP_CHECK(e);
+      (void)hipGetLastError();
+    }
+  }
+}
+
 int LinSys::solve_dev(real *b, const real *s, real tol, const real *warm_part, int warm_cnt,
                       real warm_scale) {
   const int gv = vec_grid(n), gnm = vec_grid((long long)n + m);
   CgCtl *c = ctl.p;
-  static const bool debug = opt_get("debug") != nullptr;
+  const bool debug = opt_debug;
+  const unsigned seq = ++cg_seq; // tags the control block and every progress word of this solve
   if (cg_x != b) { // the captured graph bakes the solution vector's address in
     if (cg_graph) (void)hipGraphExecDestroy(cg_graph);
     cg_graph = nullptr;
@@ -1314,12 +1394,28 @@ int LinSys::solve_dev(real *b, const real *s, real tol, const real *warm_part, i
     // B2 passes the warm start as `s` and asks for tol = max(1e-12, 0.2 min(tol, |s|_inf * warm_scale))
     hipLaunchKernelGGL(k_linsys_fused, dim3(1), dim3(FUSED_THREADS), 0, stream, A.view(), At.view(),
                        has_P ? P.view() : A.view(), has_P ? 1 : 0, b, s, rx.p, ry.p, M.p, p.p, r.p, Gp.p, z.p, tmp.p,
-                       c, tol, warm_part ? 1 : 0, warm_scale, 10LL * n);
-    HIP_CHECK(hipMemcpyAsync(hctl.p, c, sizeof(CgCtl), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+                       c, tol, warm_part ? 1 : 0, warm_scale, 10LL * n, seq, prog_dev);
+    int fits = 0;
+    if (prog_dev) { // the kernel's last store says "done, after so many iterations": no read-back, no synchronisation
+      cg_word w = progress_word();
+      while ((unsigned)(w >> 32) != seq || !(w & 1)) {
+        if (!wait_word(w, 0)) { // the kernel has left the stream: its word is in host memory
+          w = progress_word();
+          if ((unsigned)(w >> 32) != seq || !(w & 1)) throw HipError("scs_amd: the fused PCG kernel finished without publishing its result");
+        } else {
+          w = progress_word();
+        }
+      }
+      fits = (int)((w >> 1) & 0x7fffffffULL);
+    }
+    if (!prog_dev || debug) {
+      HIP_CHECK(hipMemcpyAsync(hctl.p, c, sizeof(CgCtl), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      n_syncs++;
+      fits = hctl.p->iters;
+    }
     HIP_CHECK(hipGetLastError());
     if (profiling) cg_timer.stop(cg_slot, stream);
-    const int fits = hctl.p->iters;
     if (debug)
       fprintf(stderr, "[scs_amd pcg fused] iters=%d zero=%d |r|=%.3e tol=%.3e |b|=%.3e\n", fits, hctl.p->zero_rhs,
               (double)hctl.p->norm_r, (double)hctl.p->tol, (double)hctl.p->rhs_norm);
@@ -1339,7 +1435,7 @@ int LinSys::solve_dev(real *b, const real *s, real tol, const real *warm_part, i
   if (shard) shard_allreduce(partA.p, (size_t)rhs_cnt, 1);
   hipLaunchKernelGGL(k_rhs_prep, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, b, ry.p, tmp.p, n, m, partA.p,
                      rhs_cnt, c, tol, warm_part, warm_cnt, warm_scale,
-                     (int)std::min<long long>(10LL * n, 2147483647LL));
+                     (int)std::min<long long>(10LL * n, 2147483647LL), seq, prog_dev);
   // b_x += A' R_y^-1 r_y   (private.c:305); sharded: r_x counts once (rank 0 keeps it), every slab adds its part, then the sum
   if (shard) hipLaunchKernelGGL(k_zero_unless_rank0, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, b, n, shard->rank, (const int *)&c->zero_rhs);
   {
@@ -1361,48 +1457,106 @@ int LinSys::solve_dev(real *b, const real *s, real tol, const real *warm_part, i
   }
   hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, b, s, r.p, z.p, M.p, n, partA.p,
                      partB.p, c);
-  hipLaunchKernelGGL(k_cg_start, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, p.p, z.p, n, partA.p, partB.p, gv, c);
+  hipLaunchKernelGGL(k_cg_start, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, p.p, z.p, n, partA.p, partB.p, gv, c, prog_dev);
 
-  // ---- iteration batches ---------------------------------------------------
+  // ---- iterations ----------------------------------------------------------
   const long long max_its = 10LL * n; // private.c:307
   long long it = 0;
-  int batch = std::max(4, std::min(last_its + 1, 4096));
   // partial arrays: partA <- p'Gp (K2), partB <- z'r and partB+PART_CAP/2 <- |r| (K3)
   if (use_cg2) { // iteration 0 has no update to fold in; everything after it is k_cg2_a + the transposed product
     enqueue_cg2_iteration(0);
     it = 1;
   }
   if (use_graph && !profiling && !cg_graph_tried) build_cg_graph();
-  for (;;) {
-    // cg2: the update/direction of iteration j runs inside iteration j+1's first kernel, so one more is enqueued
-    const int extra = (use_cg2 || use_cg3) ? 1 : 0; // the launch that evaluates the last iteration's stop test
-    int nb = (int)std::min<long long>(batch + (use_cg3 ? 1 : 0), max_its + extra - it);
-    if (nb < 1) nb = 1;
-    if (cg_graph && !profiling) {
-      // whole graphs only (the parity of the double-buffered z'r slot restarts with each graph);
-      // iterations enqueued past convergence are no-ops, as with individual launches
-      const int ng = (nb + CG_GRAPH_ITERS - 1) / CG_GRAPH_ITERS;
-      for (int g = 0; g < ng; ++g) HIP_CHECK(hipGraphLaunch(cg_graph, stream));
-      n_graph_launches += ng;
-      nb = ng * CG_GRAPH_ITERS;
+  // cg2: the update/direction of iteration j runs inside iteration j+1's first kernel, so one more is enqueued
+  const int extra = (use_cg2 || use_cg3) ? 1 : 0; // the launch that evaluates the last iteration's stop test
+  const bool graphs = cg_graph && !profiling;
+  // n launches of the quantum: whole graphs only (the parity of the double-buffered z'r slot restarts with each graph), or single
+  // iterations; what is enqueued past convergence is a no-op either way
+  auto enqueue = [&](int quanta) {
+    if (graphs) {
+      for (int g = 0; g < quanta; ++g) HIP_CHECK(hipGraphLaunch(cg_graph, stream));
+      n_graph_launches += quanta;
+      quanta *= CG_GRAPH_ITERS;
     } else {
-      for (int j = 0; j < nb; ++j) {
+      for (int j = 0; j < quanta; ++j) {
         if (use_cg2) enqueue_cg2_iteration(it + j);
         else if (use_cg3) enqueue_cg3_iteration(it + j);
         else enqueue_cg_iteration((int)((it + j) & 1));
       }
     }
-    it += nb;
-    HIP_CHECK(hipMemcpyAsync(hctl.p, c, sizeof(CgCtl), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    it += quanta;
+    n_enq_its += quanta;
+  };
+  int its = 0;
+  if (prog_dev) {
+    // Paced by device progress (cg_pace=1).  The host needs one fact from a linear solve -- "has it stopped, and after how many
+    // iterations" -- and reads it from the progress word the device publishes after every iteration, without a copy and without a
+    // synchronisation.  It keeps the queue at most `cg_lead` quanta (one iteration, or one graph of CG_GRAPH_ITERS) ahead of the
+    // published count: far enough that the GPU never waits for a launch, near enough that at most `cg_lead` quanta are enqueued
+    // past convergence -- and what follows the solve (the back-substitution, the rest of the ADMM step) queues right behind those.
+    // Waiting (wait_word): poll the word and yield; after CG_PACE_SPIN empty polls in a row sleep half of the iteration time
+    // observed so far in this solve (a batch run keeps 4 host threads per GPU: no busy-spinning); about once a millisecond ask
+    // the stream -- an error is raised, and an idle stream whose word says "not done" means the queue ran dry: keep enqueuing.
+    const long long Q = graphs ? CG_GRAPH_ITERS : 1, cap = max_its + extra;
+    long long pub = 0, pub0 = -1;
+    std::chrono::steady_clock::time_point t0;
+    double iter_us = 0;
+    for (;;) {
+      const cg_word w = progress_word();
+      bool done = false;
+      if ((unsigned)(w >> 32) == seq) { // else: still the previous solve's last word
+        pub = (long long)((w >> 1) & 0x7fffffffULL);
+        done = (w & 1) != 0;
+      }
+      if (done) break;
+      if (it < cap && it - extra - pub < (long long)cg_lead * Q) {
+        enqueue(1);
+        continue;
+      }
+      if (pub > 0) { // iteration time of this solve so far, for the length of the sleeps
+        const auto now = std::chrono::steady_clock::now();
+        if (pub0 < 0) {
+          pub0 = pub;
+          t0 = now;
+        } else if (pub > pub0) {
+          iter_us = std::chrono::duration<double, std::micro>(now - t0).count() / (double)(pub - pub0);
+        }
+      }
+      if (!wait_word(w, iter_us) && progress_word() == w) { // queue dry, word unchanged
+        if (it >= cap + Q) throw HipError("scs_amd: the PCG iterations finished without publishing a result");
+        enqueue(1);
+      }
+    }
+    its = (int)pub;
+    if (debug || opt_trace_file) { // the other fields of the control block: diagnostics only
+      HIP_CHECK(hipMemcpyAsync(hctl.p, c, sizeof(CgCtl), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      n_syncs++;
+    }
     if (debug)
       fprintf(stderr, "[scs_amd pcg] enq=%lld iters=%d done=%d zero=%d |r|=%.3e tol=%.3e ztr=(%.3e,%.3e) |b|=%.3e\n",
               it, hctl.p->iters, hctl.p->cg_done, hctl.p->zero_rhs, (double)hctl.p->norm_r,
               (double)hctl.p->tol, (double)hctl.p->ztr[0], (double)hctl.p->ztr[1], (double)hctl.p->rhs_norm);
-    if (hctl.p->cg_done || it >= max_its + extra) break;
-    batch = std::max(4, std::min(last_its / 4 + 1, 1024));
+  } else {
+    // Batches (cg_pace=0, row-sharded workspaces): guess the count from the previous solve, read the control block back, repeat
+    int batch = std::max(4, std::min(last_its + 1, 4096));
+    for (;;) {
+      int nb = (int)std::min<long long>(batch + (use_cg3 ? 1 : 0), max_its + extra - it);
+      if (nb < 1) nb = 1;
+      enqueue(graphs ? (nb + CG_GRAPH_ITERS - 1) / CG_GRAPH_ITERS : nb);
+      HIP_CHECK(hipMemcpyAsync(hctl.p, c, sizeof(CgCtl), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      n_syncs++;
+      if (debug)
+        fprintf(stderr, "[scs_amd pcg] enq=%lld iters=%d done=%d zero=%d |r|=%.3e tol=%.3e ztr=(%.3e,%.3e) |b|=%.3e\n",
+                it, hctl.p->iters, hctl.p->cg_done, hctl.p->zero_rhs, (double)hctl.p->norm_r,
+                (double)hctl.p->tol, (double)hctl.p->ztr[0], (double)hctl.p->ztr[1], (double)hctl.p->rhs_norm);
+      if (hctl.p->cg_done || it >= max_its + extra) break;
+      batch = std::max(4, std::min(last_its / 4 + 1, 1024));
+    }
+    its = hctl.p->iters;
   }
-  const int its = hctl.p->iters;
   n_matvecs += its;
   // y = R_y^-1 (A x - r_y)   (private.c:313-317)
   {
@@ -1411,10 +1565,11 @@ int LinSys::solve_dev(real *b, const real *s, real tol, const real *warm_part, i
   }
   if (profiling) cg_timer.stop(cg_slot, stream);
   HIP_CHECK(hipGetLastError());
-  if (const char *tf = opt_get("trace_file")) { // same record as oracle/trace_linsys.c
+  if (const char *tf = opt_trace_file) { // same record as oracle/trace_linsys.c
     real x0 = 0;
     HIP_CHECK(hipMemcpyAsync(&x0, b, sizeof(real), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
+    n_syncs++;
     if (FILE *f = fopen(tf, n_solves == 0 ? "w" : "a")) {
       fprintf(f, "%lld tol=%.17g nb=%.17g its=%d x0=%.17g\n", n_solves, (double)hctl.p->tol,
               (double)hctl.p->rhs_norm, its, (double)x0);
@@ -1584,7 +1739,7 @@ scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B
       const int W = multi_width(K);
       ls.ensure_multi(W);
       MultiWork &mw = *ls.multi;
-      const int g = vec_grid((long long)(n + m));
+      const int g = ls.vec_grid((long long)(n + m));
       if (Sc) { // staged column-major in z, transposed into s on the device
         HIP_CHECK(hipMemcpy2DAsync(mw.z.p, n * sz, Sc, (size_t)lds * sz, n * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
         MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.z.p, mw.s.p, (int)n,
@@ -1697,6 +1852,11 @@ scs_int scs_amd_linsys_sync(ScsLinSysWork *w) {
 
 void scs_amd_linsys_set_profiling(ScsLinSysWork *w, scs_int on) {
   if (w) w->ls.profiling = on != 0;
+}
+
+void scs_amd_linsys_get_cg_pacing(const ScsLinSysWork *w, long long out[4]) {
+  if (!w || !out) return;
+  w->ls.get_cg_pacing(out);
 }
 
 void scs_amd_linsys_get_stats(const ScsLinSysWork *w, ScsAmdStats *out) {

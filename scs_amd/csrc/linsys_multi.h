@@ -341,7 +341,8 @@ void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *ite
                                        mw.z.p, M.p, n, mw.part_ztr.p, mw.part_max.p, c));
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_start<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                        mw.part_max.p, gv, c));
-  // iteration batches: one control record read per batch, as in solve_dev
+  // iteration batches: one control record read per batch, as solve_dev does with cg_pace=0 (every column's own count has to be
+  // read back after the solve anyway, and the all-stopped word would need a maximum over the columns to pace by: left on batches)
   const int gp = spmm_grid(At.rows, W);
   long long it = 0;
   int batch = std::max(4, std::min(mw.last_its + 1, 4096));
