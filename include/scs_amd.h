@@ -370,6 +370,43 @@ scs_int scs_amd_solve_end(ScsWork *w, ScsSolution *sol, ScsInfo *info);
 /* test hook: every per-iteration linear solve uses this tolerance instead of the
  * schedule of src/scs.c:745-762 (0 restores the schedule) */
 void scs_amd_set_cg_tol_override(ScsWork *w, double tol);
+/* ---- a family of problems: the same A, P and cones with nprob different (b, c), solved in ONE device-resident ADMM loop ----
+ * K solves of scs_update(w, B[:,k], Cc[:,k]); scs_solve(w, &sols[k], &infos[k], warm_start)  (src/scs.c:1287-1325, :1327-1484)
+ * on one workspace, on blocks: the block solve (scs_amd_solve_lin_sys_multi) and the block projection
+ * (scs_amd_cone_proj_dual_multi) are the two halves of its iteration, in their device layout (row-major, element (i, k) at
+ * i * W + k, W in {2, 4, 8, 16}).
+ * Column k is the reference's ADMM map (src/scs.c:1356-1455) applied to problem k alone: its own tau, kappa, root_plus,
+ * primal_scale / dual_scale (normalize_b_c per column), g = (R + M)^-1 [c_k; -b_k], residuals, CG tolerance schedule
+ * (:745-762, from that column's own norms), convergence test, status, certificates and ScsInfo.  The columns share A, P, D, E,
+ * diag_r and the cones and nothing else.  Not bit for bit the single solve (the reduction trees differ); within one width the
+ * bits of a column depend neither on the other columns nor on its position, and two calls on the same inputs return the same
+ * bits (no floating-point atomics; every family solve starts its PSD eigenbases and box Newton starts cold).
+ * Convergence is tested where the single solve tests it (every 25 iterations), for all running columns in one block residual
+ * evaluation.  A column whose test fires at iteration i is frozen there with info.iter = i, exactly as the single loop breaks:
+ * from then on nothing of it is read or written, and it costs no linear-solve iteration.  The loop ends when every column is
+ * frozen, at max_iters, at time_limit_secs (one clock per chunk) or on SIGINT (every column not yet finished: SCS_SIGINT).
+ * B: host, column-major, m x nprob, leading dimension ldb >= m.  Cc: host, column-major, n x nprob, ldc >= n.  sols, infos: nprob
+ * of each; sols[k].x / y / s are caller-allocated (n, m, m) and, with warm_start != 0, hold the warm start of column k as
+ * scs_solve takes it (src/scs.c:660-687).  More than 16 problems are served in chunks of at most 16 (a chunk of one problem as
+ * a block of width 2: it stays off the single-solve state).
+ * Requires adaptive_scale == 0 (a scale update changes diag_r, which the columns share), acceleration_lookback == 0 and
+ * log_csv_filename == NULL: otherwise the call is refused before any device call with a message that names the setting
+ * (scs_amd_solve_family_refusal returns that message, or NULL).  Refused settings and bad arguments (w, B, Cc, sols or infos
+ * NULL, nprob < 1, ldb < m, ldc < n) return SCS_FAILED with sols / infos untouched.
+ * Family state (block iterates, residual blocks, per-column b, c, scales) belongs to this entry: allocated at the first call at
+ * the largest width used, freed by scs_finish.  The workspace's own problem and single-solve state (b, c, scales, iterates,
+ * cone and PCG state of the single-vector path) are neither read nor written: a scs_solve after a family call returns the
+ * bits it returns without it.  scs_amd_set_cg_tol_override applies per column.  infos[k].solve_time, lin_sys_time and cone_time
+ * are the chunk's wall times, the same in every column of a chunk; scale_updates and the acceleration fields are 0.  verbose
+ * prints the header once and one summary line per column, no iteration table.
+ * Returns 0 when every column ended with a status the single solve would have returned; SCS_FAILED on a HIP failure (message on
+ * stderr, every column NaN-filled with status SCS_FAILED, the workspace stays usable). */
+scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob,
+                             const scs_float *B, scs_int ldb,   /* host, column-major, m x nprob, ldb >= m */
+                             const scs_float *Cc, scs_int ldc,  /* host, column-major, n x nprob, ldc >= n */
+                             ScsSolution *sols, ScsInfo *infos, /* nprob of each; sols[k].x/y/s caller-allocated */
+                             scs_int warm_start);
+const char *scs_amd_solve_family_refusal(const ScsWork *w);
 /* What scs_init decided about its internal numbering (scs_amd/csrc/reorder.h: variables, the rows of the zero / nonnegative
  * cones and -- round 6 -- the rows behind the first one of a second-order cone may be renumbered so that the gathers of the CSR products of linsys/scs_matrix.c:161-186 share cache lines; callers never see
  * it -- b, c, warm starts and the returned (x, y, s) are mapped at this boundary).  out[0] = 1 if renumbered, out[1], out[2] =

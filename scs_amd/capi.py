@@ -203,6 +203,12 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_solve_end.argtypes = [C.c_void_p, C.POINTER(T.ScsSolution), C.POINTER(T.ScsInfo)]
             lib.scs_amd_set_cg_tol_override.restype = None
             lib.scs_amd_set_cg_tol_override.argtypes = [C.c_void_p, C.c_double]
+            # a family of problems in one loop (include/scs_amd.h)
+            lib.scs_amd_solve_family.restype = scs_int
+            lib.scs_amd_solve_family.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, C.POINTER(T.ScsSolution),
+                                                 C.POINTER(T.ScsInfo), scs_int]
+            lib.scs_amd_solve_family_refusal.restype = C.c_char_p
+            lib.scs_amd_solve_family_refusal.argtypes = [C.c_void_p]
             # one linear system split by rows across GPUs, native form (scs_amd/csrc/shard_native.cpp)
             lib.scs_amd_shard_unique_id.restype = scs_int
             lib.scs_amd_shard_unique_id.argtypes = [C.c_char_p]
@@ -419,3 +425,30 @@ def solve(lib, prob, settings=None, warm=None, want_stats=False, profiling=False
     finally:
         lib.scs_finish(w)
     return out
+
+
+def solve_family(lib, w, B, Cc, warm=None, warm_start=None):
+    """scs_amd_solve_family on an initialised workspace `w`.  B (m x K), Cc (n x K): anything numpy turns into 2-D arrays;
+    they are passed column-major.  warm: (X, Y, S) of shapes n x K, m x K, m x K, or None.  Returns (rc, list of K dicts
+    in the shape of `solve`); the arrays of a refused call come back as they went in (zeros, or the warm start)."""
+    T = lib._scs_types
+    f = T.np_float
+    B = np.asfortranarray(np.asarray(B, dtype=f))
+    Cc = np.asfortranarray(np.asarray(Cc, dtype=f))
+    if B.ndim != 2 or Cc.ndim != 2 or B.shape[1] != Cc.shape[1]:
+        raise ValueError("B must be m x K and C n x K")
+    m, K = B.shape
+    n = Cc.shape[0]
+    X, Y, S = (np.zeros((n, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"))
+    if warm is not None:
+        X[:], Y[:], S[:] = warm
+    sols = (T.ScsSolution * max(K, 1))()
+    infos = (T.ScsInfo * max(K, 1))()
+    sz = np.dtype(f).itemsize
+    for k in range(K):
+        sols[k].x = C.cast(X.ctypes.data + k * n * sz, T.fp)
+        sols[k].y = C.cast(Y.ctypes.data + k * m * sz, T.fp)
+        sols[k].s = C.cast(S.ctypes.data + k * m * sz, T.fp)
+    ws = (1 if warm is not None else 0) if warm_start is None else int(warm_start)
+    rc = lib.scs_amd_solve_family(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos, ws)
+    return rc, [dict(x=X[:, k].copy(), y=Y[:, k].copy(), s=S[:, k].copy(), info=info_dict(infos[k])) for k in range(K)]

@@ -345,6 +345,9 @@ struct Resid { // reference include/scs_work.h:32-52 (scalars) + the norms the l
   real nm_ax_s_btau = 0, nm_px_aty_ctau = 0, nm_ax_s = 0, nm_ax = 0, nm_px = 0, nm_aty = 0, nm_s = 0;
 };
 
+struct FamilyWork;                  // admm_multi.h: state of scs_amd_solve_family, allocated by its first call
+static void family_free(FamilyWork *f);
+
 struct SCS_WORK {
   int n = 0, m = 0, l = 0, device = 0;
   ScsSettings stgs;
@@ -392,7 +395,9 @@ struct SCS_WORK {
   EventTimer cone_timer;
   bool profiling = false;
   long long cone_projs = 0;
+  FamilyWork *fam = nullptr;
   ~SCS_WORK() {
+    family_free(fam);
     if (log_csv_fout) fclose(log_csv_fout);
     if (accel) aa_host_finish(accel);
     if (accel_dev) aa_dev_finish(accel_dev);
@@ -491,6 +496,57 @@ static void compute_residuals_scalars(Resid *r, real pd) { // :463-485
   if (r->bty_tau < -tol) r->res_infeas = safediv_pos(r->nm_aty, -r->bty_tau);
 }
 
+// the scalar half of populate_residual_struct + unnormalize_residuals (:487-531) for one problem: q holds the reduced
+// quantities Q_* at stride qs (1 for the single solve; the block width for a column of a family), ps / ds that problem's scales
+static void fill_residuals(Resid &r, Resid &o, const real *q, int qs, int iter, bool has_P, bool normalize, real ps, real ds) {
+  r.last_iter = iter;
+  r.tau = q[Q_TAU * qs];
+  r.kap = q[Q_KAP * qs];
+  r.nm_ax_s_btau = q[Q_PRI_N * qs];
+  r.nm_ax_s = q[Q_AXS_N * qs];
+  r.nm_ax = q[Q_AX_N * qs];
+  r.nm_s = q[Q_S_N * qs];
+  r.nm_px_aty_ctau = q[Q_DUAL_N * qs];
+  r.nm_px = q[Q_PX_N * qs];
+  r.nm_aty = q[Q_ATY_N * qs];
+  r.xt_p_x_tau = has_P ? q[Q_XPX * qs] : (real)0;
+  r.bty_tau = q[Q_BTY * qs];
+  r.ctx_tau = q[Q_CTX * qs];
+  r.bty = safediv_pos(r.bty_tau, r.tau);
+  r.ctx = safediv_pos(r.ctx_tau, r.tau);
+  r.xt_p_x = safediv_pos(r.xt_p_x_tau, r.tau * r.tau);
+  r.gap = std::fabs(r.xt_p_x + r.ctx + r.bty);
+  r.pobj = r.xt_p_x / (real)2. + r.ctx;
+  r.dobj = -r.xt_p_x / (real)2. - r.bty;
+  compute_residuals_scalars(&r, (real)1.0);
+  // unnormalize_residuals (:487-531)
+  if (normalize) {
+    const real pd = ps * ds;
+    o.last_iter = iter;
+    o.tau = r.tau;
+    o.kap = r.kap / pd;
+    o.bty_tau = r.bty_tau / pd;
+    o.ctx_tau = r.ctx_tau / pd;
+    o.xt_p_x_tau = r.xt_p_x_tau / pd;
+    o.xt_p_x = r.xt_p_x / pd;
+    o.ctx = r.ctx / pd;
+    o.bty = r.bty / pd;
+    o.pobj = r.pobj / pd;
+    o.dobj = r.dobj / pd;
+    o.gap = r.gap / pd;
+    o.nm_ax_s_btau = q[Q_PRI_O * qs];
+    o.nm_ax_s = q[Q_AXS_O * qs];
+    o.nm_ax = q[Q_AX_O * qs];
+    o.nm_s = q[Q_S_O * qs];
+    o.nm_px_aty_ctau = q[Q_DUAL_O * qs];
+    o.nm_px = q[Q_PX_O * qs];
+    o.nm_aty = q[Q_ATY_O * qs];
+    compute_residuals_scalars(&o, pd);
+  } else {
+    o = r;
+  }
+}
+
 static void populate_residuals(ScsWork *w, int iter) {
   if (w->r_n.last_iter == iter) return;
   const int n = w->n, m = w->m, l = w->l;
@@ -516,55 +572,7 @@ static void populate_residuals(ScsWork *w, int iter) {
       printf("WARNING: %d PSD block projection(s) hit the Jacobi sweep cap (eigenvalues may be inaccurate)\n", bad);
     w->psd_unconverged += bad;
   }
-  const real *q = w->hq.p;
-  Resid &r = w->r_n;
-  r.last_iter = iter;
-  r.tau = q[Q_TAU];
-  r.kap = q[Q_KAP];
-  r.nm_ax_s_btau = q[Q_PRI_N];
-  r.nm_ax_s = q[Q_AXS_N];
-  r.nm_ax = q[Q_AX_N];
-  r.nm_s = q[Q_S_N];
-  r.nm_px_aty_ctau = q[Q_DUAL_N];
-  r.nm_px = q[Q_PX_N];
-  r.nm_aty = q[Q_ATY_N];
-  r.xt_p_x_tau = w->has_P ? q[Q_XPX] : (real)0;
-  r.bty_tau = q[Q_BTY];
-  r.ctx_tau = q[Q_CTX];
-  r.bty = safediv_pos(r.bty_tau, r.tau);
-  r.ctx = safediv_pos(r.ctx_tau, r.tau);
-  r.xt_p_x = safediv_pos(r.xt_p_x_tau, r.tau * r.tau);
-  r.gap = std::fabs(r.xt_p_x + r.ctx + r.bty);
-  r.pobj = r.xt_p_x / (real)2. + r.ctx;
-  r.dobj = -r.xt_p_x / (real)2. - r.bty;
-  compute_residuals_scalars(&r, (real)1.0);
-  // unnormalize_residuals (:487-531)
-  Resid &o = w->r_o;
-  if (w->stgs.normalize) {
-    const real pd = ps * ds;
-    o.last_iter = iter;
-    o.tau = r.tau;
-    o.kap = r.kap / pd;
-    o.bty_tau = r.bty_tau / pd;
-    o.ctx_tau = r.ctx_tau / pd;
-    o.xt_p_x_tau = r.xt_p_x_tau / pd;
-    o.xt_p_x = r.xt_p_x / pd;
-    o.ctx = r.ctx / pd;
-    o.bty = r.bty / pd;
-    o.pobj = r.pobj / pd;
-    o.dobj = r.dobj / pd;
-    o.gap = r.gap / pd;
-    o.nm_ax_s_btau = q[Q_PRI_O];
-    o.nm_ax_s = q[Q_AXS_O];
-    o.nm_ax = q[Q_AX_O];
-    o.nm_s = q[Q_S_O];
-    o.nm_px_aty_ctau = q[Q_DUAL_O];
-    o.nm_px = q[Q_PX_O];
-    o.nm_aty = q[Q_ATY_O];
-    compute_residuals_scalars(&o, pd);
-  } else {
-    o = r;
-  }
+  fill_residuals(w->r_n, w->r_o, w->hq.p, 1, iter, w->has_P, w->stgs.normalize != 0, ps, ds);
 }
 
 // ---- per-iteration CSV log: column set, order and formats of src/rw.c:707-863 ----------
@@ -722,13 +730,13 @@ static const char *LOG_CSV_HEADER =
     "accepted_accel_steps,rejected_accel_steps,time,spectral_Newton_iter,plain_Newton_success,res_dual_spectral,"
     "res_pri_spectral,comp_spectral,\n";
 
-static int has_converged(ScsWork *w) { // :611-649
-  const Resid &r = w->r_o;
-  const real eps_abs = w->stgs.eps_abs, eps_rel = w->stgs.eps_rel, eps_infeas = w->stgs.eps_infeas;
+// r: the un-normalised residuals of one problem; nm_b_orig / nm_c_orig: |b|_inf, |c|_inf of that problem as given
+static int has_converged(const Resid &r, const ScsSettings &stgs, real nm_b_orig, real nm_c_orig) { // :611-649
+  const real eps_abs = stgs.eps_abs, eps_rel = stgs.eps_rel, eps_infeas = stgs.eps_infeas;
   if (r.tau > (real)0.) {
     const real grl = std::max(std::max(std::fabs(r.xt_p_x), std::fabs(r.ctx)), std::fabs(r.bty));
-    const real prl = std::max(std::max(w->nm_b_orig * r.tau, r.nm_s), r.nm_ax) / r.tau;
-    const real drl = std::max(std::max(w->nm_c_orig * r.tau, r.nm_px), r.nm_aty) / r.tau;
+    const real prl = std::max(std::max(nm_b_orig * r.tau, r.nm_s), r.nm_ax) / r.tau;
+    const real drl = std::max(std::max(nm_c_orig * r.tau, r.nm_px), r.nm_aty) / r.tau;
     if (std::isless(r.res_pri, eps_abs + eps_rel * prl) && std::isless(r.res_dual, eps_abs + eps_rel * drl) &&
         std::isless(r.gap, eps_abs + eps_rel * grl))
       return SCS_SOLVED;
@@ -806,12 +814,14 @@ static void print_header(const ScsWork *w) {
   printf(" iter | pri res | dua res |   gap   |   obj   |  scale  | time (s)\n");
   print_rule();
 }
-static void print_summary(const ScsWork *w, int i, double t0) {
-  const Resid &r = w->r_o;
+static void print_summary_row(const Resid &r, int i, real scale, double secs) {
   // scs.c:207-219: total time including setup
   printf("%*i|%*.2e %*.2e %*.2e %*.2e %*.2e %*.2e \n", 6, i, 9, (double)r.res_pri, 9, (double)r.res_dual, 9, (double)r.gap, 9,
-         (double)(0.5 * (r.pobj + r.dobj)), 9, (double)w->stgs.scale, 9, (now_ms() - t0 + w->setup_time) / 1e3);
+         (double)(0.5 * (r.pobj + r.dobj)), 9, (double)scale, 9, secs);
   fflush(stdout);
+}
+static void print_summary(const ScsWork *w, int i, double t0) {
+  print_summary_row(w->r_o, i, w->stgs.scale, (now_ms() - t0 + w->setup_time) / 1e3);
 }
 static void print_footer(const ScsInfo *info) { // scs.c:246-272
   print_rule();
@@ -836,57 +846,85 @@ static void fill_nan(real *p, int len) {
 static void scale_vec(real *p, real a, int len) {
   for (int i = 0; i < len; ++i) p[i] *= a;
 }
-static void set_solved(const ScsWork *w, ScsSolution *sol, ScsInfo *info) {
-  const real it = safediv_pos((real)1.0, w->r_o.tau);
-  scale_vec(sol->x, it, w->n);
-  scale_vec(sol->y, it, w->m);
-  scale_vec(sol->s, it, w->m);
-  info->gap = w->r_o.gap;
-  info->res_pri = w->r_o.res_pri;
-  info->res_dual = w->r_o.res_dual;
-  info->pobj = w->r_o.xt_p_x / (real)2. + w->r_o.ctx;
-  info->dobj = -w->r_o.xt_p_x / (real)2. - w->r_o.bty;
+// r: the un-normalised residuals of the problem whose (x, y, s) sol holds
+static void set_solved(const Resid &r, int n, int m, ScsSolution *sol, ScsInfo *info) {
+  const real it = safediv_pos((real)1.0, r.tau);
+  scale_vec(sol->x, it, n);
+  scale_vec(sol->y, it, m);
+  scale_vec(sol->s, it, m);
+  info->gap = r.gap;
+  info->res_pri = r.res_pri;
+  info->res_dual = r.res_dual;
+  info->pobj = r.xt_p_x / (real)2. + r.ctx;
+  info->dobj = -r.xt_p_x / (real)2. - r.bty;
   strcpy(info->status, "solved");
   info->status_val = SCS_SOLVED;
 }
-static void set_infeasible(const ScsWork *w, ScsSolution *sol, ScsInfo *info) {
-  scale_vec(sol->y, (real)-1 / w->r_o.bty_tau, w->m);
-  fill_nan(sol->x, w->n);
-  fill_nan(sol->s, w->m);
+static void set_infeasible(const Resid &r, int n, int m, ScsSolution *sol, ScsInfo *info) {
+  scale_vec(sol->y, (real)-1 / r.bty_tau, m);
+  fill_nan(sol->x, n);
+  fill_nan(sol->s, m);
   info->gap = info->res_pri = info->res_dual = (real)NAN;
   info->pobj = info->dobj = (real)INFINITY;
   strcpy(info->status, "infeasible");
   info->status_val = SCS_INFEASIBLE;
 }
-static void set_unbounded(const ScsWork *w, ScsSolution *sol, ScsInfo *info) {
-  scale_vec(sol->x, (real)-1 / w->r_o.ctx_tau, w->n);
-  scale_vec(sol->s, (real)-1 / w->r_o.ctx_tau, w->m);
-  fill_nan(sol->y, w->m);
+static void set_unbounded(const Resid &r, int n, int m, ScsSolution *sol, ScsInfo *info) {
+  scale_vec(sol->x, (real)-1 / r.ctx_tau, n);
+  scale_vec(sol->s, (real)-1 / r.ctx_tau, m);
+  fill_nan(sol->y, m);
   info->gap = info->res_pri = info->res_dual = (real)NAN;
   info->pobj = info->dobj = -(real)INFINITY;
   strcpy(info->status, "unbounded");
   info->status_val = SCS_UNBOUNDED;
 }
-static void set_unfinished(const ScsWork *w, ScsSolution *sol, ScsInfo *info) {
-  const Resid &r = w->r_o;
+// how the loop ended, for the wording of an unfinished status
+struct LoopEnd {
+  int max_iters, time_limit_reached;
+  bool stepped;
+};
+static void set_unfinished(const Resid &r, int n, int m, const LoopEnd &e, ScsSolution *sol, ScsInfo *info) {
   if (r.kap > r.tau && (r.bty_tau < 0 || r.ctx_tau < 0)) {
     if (r.bty_tau < 0 && r.bty_tau < r.ctx_tau) {
-      set_infeasible(w, sol, info);
+      set_infeasible(r, n, m, sol, info);
       info->status_val = SCS_INFEASIBLE_INACCURATE;
     } else {
-      set_unbounded(w, sol, info);
+      set_unbounded(r, n, m, sol, info);
       info->status_val = SCS_UNBOUNDED_INACCURATE;
     }
   } else if (r.tau > 0) {
-    set_solved(w, sol, info);
+    set_solved(r, n, m, sol, info);
     info->status_val = SCS_SOLVED_INACCURATE;
   } else {
     printf("ERROR: could not determine problem status.\n");
     info->status_val = SCS_FAILED;
   }
-  if (w->time_limit_reached) strcat(info->status, " (inaccurate - reached time_limit_secs)");
-  else if (info->iter >= w->stgs.max_iters || w->stepped) strcat(info->status, " (inaccurate - reached max_iters)");
+  if (e.time_limit_reached) strcat(info->status, " (inaccurate - reached time_limit_secs)");
+  else if (info->iter >= e.max_iters || e.stepped) strcat(info->status, " (inaccurate - reached max_iters)");
   else printf("ERROR: should not be in this state (1).\n");
+}
+
+// the end of finalize (:825-969) for one problem: sol holds its un-normalised (x, y, s), info->iter and info->status_val are set
+static void finalize_status(const Resid &r, int n, int m, const LoopEnd &e, ScsSolution *sol, ScsInfo *info) {
+  real nm_s = 0, nm_y = 0, sty = 0;
+  for (int i = 0; i < m; ++i) {
+    nm_s = std::max(nm_s, (real)std::fabs(sol->s[i]));
+    nm_y = std::max(nm_y, (real)std::fabs(sol->y[i]));
+    sty += sol->s[i] * sol->y[i];
+  }
+  info->res_infeas = r.res_infeas;
+  info->res_unbdd_a = r.res_unbdd_a;
+  info->res_unbdd_p = r.res_unbdd_p;
+  info->comp_slack = std::fabs(sty);
+  if (info->comp_slack > (real)1e-5 * std::max(nm_s, nm_y))
+    printf("WARNING - large complementary slackness residual: %f\n", (double)info->comp_slack);
+  switch (info->status_val) {
+  case SCS_SOLVED: set_solved(r, n, m, sol, info); break;
+  case SCS_INFEASIBLE: set_infeasible(r, n, m, sol, info); break;
+  case SCS_UNBOUNDED: set_unbounded(r, n, m, sol, info); break;
+  case SCS_UNFINISHED: set_unfinished(r, n, m, e, sol, info); break;
+  default: printf("ERROR: should not be in this state (2).\n");
+  }
 }
 
 static void finalize(ScsWork *w, ScsSolution *sol, ScsInfo *info, int iter) {
@@ -916,17 +954,8 @@ static void finalize(ScsWork *w, ScsSolution *sol, ScsInfo *info, int iter) {
     if (w->stgs.normalize) un_normalize_sol(w->scal, sol->x, sol->y, sol->s);
   }
   populate_residuals(w, iter);
-  real nm_s = 0, nm_y = 0, sty = 0;
-  for (int i = 0; i < m; ++i) {
-    nm_s = std::max(nm_s, (real)std::fabs(sol->s[i]));
-    nm_y = std::max(nm_y, (real)std::fabs(sol->y[i]));
-    sty += sol->s[i] * sol->y[i];
-  }
   info->setup_time = (real)w->setup_time;
   info->iter = iter;
-  info->res_infeas = w->r_o.res_infeas;
-  info->res_unbdd_a = w->r_o.res_unbdd_a;
-  info->res_unbdd_p = w->r_o.res_unbdd_p;
   info->scale = w->stgs.scale;
   info->scale_updates = w->scale_updates;
   info->rejected_accel_steps = w->rejected_accel_steps;
@@ -935,16 +964,8 @@ static void finalize(ScsWork *w, ScsSolution *sol, ScsInfo *info, int iter) {
   info->aa_stats.last_aa_norm = (real)NAN;
   if (w->accel) aa_host_stats(w->accel, &info->aa_stats);
   if (w->accel_dev) aa_dev_stats(w->accel_dev, &info->aa_stats);
-  info->comp_slack = std::fabs(sty);
-  if (info->comp_slack > (real)1e-5 * std::max(nm_s, nm_y))
-    printf("WARNING - large complementary slackness residual: %f\n", (double)info->comp_slack);
-  switch (info->status_val) {
-  case SCS_SOLVED: set_solved(w, sol, info); break;
-  case SCS_INFEASIBLE: set_infeasible(w, sol, info); break;
-  case SCS_UNBOUNDED: set_unbounded(w, sol, info); break;
-  case SCS_UNFINISHED: set_unfinished(w, sol, info); break;
-  default: printf("ERROR: should not be in this state (2).\n");
-  }
+  const LoopEnd e{(int)w->stgs.max_iters, w->time_limit_reached, w->stepped};
+  finalize_status(w->r_o, n, m, e, sol, info);
 }
 
 // ---- ctrl-c support (behaviour of src/ctrlc.c:84-125): while at least one solve is in
@@ -1350,7 +1371,7 @@ static int solve_steps(ScsWork *w, int upto) {
     if (check) {
       if (interrupted()) return -2; // :1400-1403
       populate_residuals(w, i);
-      if ((w->run_status = has_converged(w)) != 0) {
+      if ((w->run_status = has_converged(w->r_o, w->stgs, w->nm_b_orig, w->nm_c_orig)) != 0) {
         w->loop_done = true;
         break; // like the reference, the converged iteration is not counted (:1405-1407)
       }
@@ -1652,3 +1673,5 @@ void scs_amd_get_stats(const ScsWork *cw, ScsAmdStats *out) {
 }
 
 } // extern "C"
+
+#include "admm_multi.h" // families of problems: K solves in one loop on blocks

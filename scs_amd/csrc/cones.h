@@ -80,6 +80,8 @@ struct ConeDev {
   ConeMulti *multi = nullptr;
   void ensure_multi(int W);
   void proj_dual_multi(real *X, int W, int K, const real *r_y);
+  void proj_primal_multi(real *X, int W, int K, const real *r_y); // the same without the Moreau wrapper: Proj_K per column
+  void reset_multi_cold();                                        // box Newton starts and eigenbases of the block state: cold
   // launches shared by the two paths
   void launch_box(real *tx, real *t_warm, const real *rb);
   void launch_psd_lds(real *cw, int nblocks, const int *off, const int *kk, real *tscratch, real *vprev, int warm);

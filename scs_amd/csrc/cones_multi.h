@@ -330,6 +330,27 @@ void ConeDev::proj_dual_multi(real *X, int W, int K, const real *r_y) {
   ConeMulti &mc = *multi;
   const int g = small_grid((long long)m * W);
   CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_pre<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
+  proj_primal_multi(X, W, K, r_y);
+  CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_post<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
+}
+
+// the block state back to what ensure_multi leaves: every column position starts its box Newton iteration and its eigenbases cold
+void ConeDev::reset_multi_cold() {
+  if (!multi) return;
+  ConeMulti &mc = *multi;
+  const std::vector<real> ones(mc.width, (real)1); // cones.c:1560
+  mc.box_t.upload(ones.data(), mc.width, stream);
+  HIP_CHECK(hipStreamSynchronize(stream)); // `ones` ends here
+  mc.psd_calls = 0;
+  for (BigPsd *b : mc.big) b->reset_warm_start();
+}
+
+// X (device, m x W block) <- Proj_K of its columns (proj_cone, cones.c:1340-1394, per column), without the Moreau wrapper: what
+// proj_primal is to proj_dual.  The elementwise and second-order passes run over all W columns; the box cone and the PSD blocks beyond
+// the LDS path over columns 0 .. K - 1.  Padding columns that hold zeros keep them.
+void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y) {
+  ensure_multi(W);
+  ConeMulti &mc = *multi;
   if (z + l > 0)
     CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_zero_pos<MW>, dim3(small_grid((long long)(z + l) * W)), dim3(SCSAMD_BLOCK), 0, stream, X, z, l));
   if (bsize > 0) { // column after column on the column position's Newton start
@@ -364,7 +385,6 @@ void ConeDev::proj_dual_multi(real *X, int W, int K, const real *r_y) {
   if (ep + ed + psize > 0)
     CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_exp_pow<MW>, dim3(small_grid((long long)(ep + ed + psize) * W)), dim3(SCSAMD_BLOCK), 0, stream,
                                               X + (size_t)exp_off * W, ep, ed, psize, pow_a.p));
-  CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_post<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
 }
 
 } // namespace scsamd

@@ -142,7 +142,7 @@ void equilibrate(HostCsc *P, HostCsc &A, const ScsCone *k, Scaling &sc) {
 }
 
 // b <- sigma D b, c <- sigma E c with sigma = 1/clip(max(|Db|_inf, |Ec|_inf))
-void normalize_b_c(Scaling &sc, real *b, real *c) {
+real normalize_b_c_sigma(const Scaling &sc, real *b, real *c) {
   const size_t m = sc.D.size(), n = sc.E.size();
   real nb = 0, nc = 0;
   for (size_t j = 0; j < n; ++j) {
@@ -159,8 +159,9 @@ void normalize_b_c(Scaling &sc, real *b, real *c) {
   sigma = safe_div_pos((real)1, sigma);
   for (size_t j = 0; j < n; ++j) c[j] *= sigma;
   for (size_t i = 0; i < m; ++i) b[i] *= sigma;
-  sc.primal_scale = sc.dual_scale = sigma;
+  return sigma;
 }
+void normalize_b_c(Scaling &sc, real *b, real *c) { sc.primal_scale = sc.dual_scale = normalize_b_c_sigma(sc, b, c); }
 
 void normalize_sol(const Scaling &sc, real *x, real *y, real *s) {
   for (size_t j = 0; j < sc.E.size(); ++j) x[j] /= (sc.E[j] / sc.dual_scale);

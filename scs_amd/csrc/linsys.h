@@ -72,6 +72,20 @@ struct ShardHook {
   int (*allreduce)(void *ctx, real *buf, size_t count, int op /* 0 sum, 1 max */, hipStream_t st) = nullptr; // 0 = ok
 };
 
+// What a block solve works on when the caller holds the blocks (LinSys::solve_multi_blocks), all in device memory, in the layout
+// of spmm.h.  warm_part != null: the tolerance of column k is formed on the device, as solve_dev forms it, as
+//     max(1e-12, 0.2 * min(tolv[k], max(column k of warm_part[0 .. warm_cnt)) * warm_scale))      (reference src/scs.c:745-762)
+// from warm_cnt x W per-workgroup partials of |s|_inf; otherwise tolv[k] is used as given.  pre_stopped != null: W ints, a non-zero
+// entry marks a column that is stopped on entry -- its lanes load and store nothing, it costs no iteration and counts none.
+struct MultiRhs {
+  real *bx = nullptr, *by = nullptr; // n x W, m x W: [r_x; r_y] -> [x; y] in place
+  const real *s = nullptr;           // n x W warm start, or null
+  const real *warm_part = nullptr;
+  int warm_cnt = 0;
+  real warm_scale = 0;
+  const int *pre_stopped = nullptr;
+};
+
 struct LinSys {
   int n = 0, m = 0;
   ShardHook *shard = nullptr;   // non-null: this workspace holds one row slab (set_shard)
@@ -167,6 +181,7 @@ struct LinSys {
   void launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip);
   void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr);
   void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
+  void solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out);
   long long matvec_bytes() const { return A.algorithmic_bytes() + At.algorithmic_bytes(); }
   void harvest_timers();
   void get_cg_pacing(long long out[4]) const; // scs_amd_get_cg_pacing (include/scs_amd.h)

@@ -22,21 +22,6 @@ struct TolArgs {
   real t[MULTI_W_MAX];
 };
 
-// consumer side of the two-level reduction, per column: `part` holds count x W entries, entry (b, k) at b * W + k
-template <int W> __device__ __forceinline__ real reduce_partials_col_sum(const real *part, int count, real *sh) {
-  real s = 0;
-  for (int i = threadIdx.x; i < count * W; i += SCSAMD_BLOCK) s += part[i]; // SCSAMD_BLOCK % W == 0: a thread stays in its column
-  return block_col_sum<W>(s, sh);
-}
-template <int W> __device__ __forceinline__ real reduce_partials_col_max(const real *part, int count, real *sh) {
-  real s = 0;
-  for (int i = threadIdx.x; i < count * W; i += SCSAMD_BLOCK) {
-    const real v = part[i];
-    s = v > s ? v : s;
-  }
-  return block_col_max<W>(s, sh);
-}
-
 // column-major (len x K, leading dimension len) <-> block layout; padding columns become zero
 template <int W>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_to_block(const real *__restrict__ src, real *dx, int n, real *dy, int m, int K) {
@@ -85,15 +70,28 @@ __device__ __forceinline__ void set_all_done(CgCtlM *ctl, int W, bool col_done) 
 }
 
 // private.c:296-303 per column: zero short-circuit, tmp = R_y^-1 r_y; arms the control block.  Padding columns count as zero.
+// `warm_part` (or null): per-workgroup, per-column |warm start|_inf partials; with it the tolerance of column k is formed here as
+// solve_dev forms it (src/scs.c:745-762), tol.t[k] being the cap.  `pre` (W ints, or null): columns that are stopped on entry --
+// nothing of theirs is read or written, here or by any later kernel of the solve, and they count no iteration.
 template <int W>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by, const real *__restrict__ ry, real *tmp, int n, int m,
-                                                             const real *part, int pcount, CgCtlM *ctl, TolArgs tol, int K, int max_its) {
+                                                             const real *part, int pcount, CgCtlM *ctl, TolArgs tol, int K, int max_its,
+                                                             const real *warm_part, int warm_cnt, real warm_scale, const int *pre) {
   __shared__ real red[4 * W];
   const real nb = reduce_partials_col_max<W>(part, pcount, red);
   const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
   const int col = threadIdx.x & (W - 1);
-  const bool zero = col >= K || nb <= (real)1e-12;
-  if (zero) {
+  const bool stopped = pre && pre[col];
+  const bool zero = stopped || col >= K || nb <= (real)1e-12;
+  real t = col < K ? tol.t[col] : (real)0;
+  if (warm_part) {
+    const real nw = reduce_partials_col_max<W>(warm_part, warm_cnt, red) * warm_scale;
+    t = t < nw ? t : nw;
+    t = (real)0.2 * t;                     // CG_TOL_FACTOR, include/glbopts.h:250
+    t = t > (real)1e-12 ? t : (real)1e-12; // CG_BEST_TOL, glbopts.h:247
+  }
+  if (stopped) {
+  } else if (zero) {
     for (size_t f = gtid; f < (size_t)n * W; f += gs) bx[f] = 0;
     for (size_t f = gtid; f < (size_t)m * W; f += gs) {
       by[f] = 0;
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by,
       ctl->zero_rhs[col] = zero ? 1 : 0;
       ctl->done[col] = zero ? 1 : 0;
       ctl->iters[col] = 0;
-      ctl->tol[col] = col < K ? tol.t[col] : (real)0;
+      ctl->tol[col] = col < K ? t : (real)0;
       ctl->rhs_norm[col] = nb;
       ctl->norm_r[col] = 0;
       ctl->ztr[0][col] = 0;
@@ -319,6 +317,18 @@ void LinSys::mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials
 // K columns (2 <= K <= W) held in multi->bx / by (and multi->s when warm) in the block layout: [r_x; r_y] -> [x; y] in place
 void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out) {
   MultiWork &mw = *multi;
+  MultiRhs a;
+  a.bx = mw.bx.p;
+  a.by = mw.by.p;
+  a.s = warm ? mw.s.p : nullptr;
+  solve_multi_blocks(K, W, a, tolv, iters_out);
+}
+
+// the same on blocks the caller holds (a.bx: n x W, a.by: m x W, a.s: n x W or null), with the options of MultiRhs (linsys.h)
+void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out) {
+  MultiWork &mw = *multi;
+  const bool warm = a.s != nullptr;
+  real *const bx = a.bx, *const by = a.by;
   const int gv = vec_grid((long long)n * W), gnm = vec_grid(((long long)n + m) * W);
   CgCtlM *c = mw.ctl.p;
   real *Gp = mw.gt.p, *tmpb = mw.gt.p + (size_t)n * mw.width;
@@ -329,15 +339,15 @@ void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *ite
   const size_t nx = (size_t)n * W, ny = (size_t)m * W;
   const long long mv0 = n_matvecs;
 
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_absmax<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, nx, mw.by.p, ny, mw.part_max.p));
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rhs_prep<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, mw.by.p, ry.p, tmpb, n, m,
-                                       mw.part_max.p, gnm, c, ta, K, max_its));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_absmax<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, nx, by, ny, mw.part_max.p));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rhs_prep<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, ry.p, tmpb, n, m,
+                                       mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
   { // b_x += A' R_y^-1 r_y   (private.c:305)
     EpiArgs e{nullptr, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_ACC, At, tmpb, mw.bx.p, e, zero, all);
+    launch_spmm(W, EPI_ACC, At, tmpb, bx, e, zero, all);
   }
-  if (warm) mat_vec_multi_dev(W, mw.s.p, mw.r.p, nullptr, zero, all); // r = G s  (private.c:153)
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_init<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, warm ? mw.s.p : nullptr, mw.r.p,
+  if (warm) mat_vec_multi_dev(W, a.s, mw.r.p, nullptr, zero, all); // r = G s  (private.c:153)
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_init<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
                                        mw.z.p, M.p, n, mw.part_ztr.p, mw.part_max.p, c));
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_start<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                        mw.part_max.p, gv, c));
@@ -352,7 +362,7 @@ void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *ite
     for (int j = 0; j < nb; ++j) {
       const int q = (int)((it + j) & 1);
       mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all);
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_update<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.bx.p, mw.r.p, mw.z.p, mw.p.p, Gp,
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_update<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p, Gp,
                                            M.p, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
       MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_direction<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                            mw.part_max.p, gv, c, q));
@@ -365,7 +375,7 @@ void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *ite
   }
   { // y = R_y^-1 (A x - r_y)   (private.c:313-317)
     EpiArgs e{ry.p, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_NEGDIV, A, mw.bx.p, mw.by.p, e, zero, nullptr);
+    launch_spmm(W, EPI_NEGDIV, A, bx, by, e, zero, nullptr);
   }
   HIP_CHECK(hipGetLastError());
   int most = 0;

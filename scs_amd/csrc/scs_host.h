@@ -103,6 +103,7 @@ void equilibrate(HostCsc *P, HostCsc &A, const ScsCone *k, Scaling &sc);
 void equilibrate_dev(HostCsc *P, HostCsc &A, const ScsCone *k, Scaling &sc, hipStream_t st,
                      CsrPattern *csr_cache);
 void normalize_b_c(Scaling &sc, real *b, real *c);
+real normalize_b_c_sigma(const Scaling &sc, real *b, real *c); // the same on D, E alone: returns primal_scale = dual_scale instead of storing it
 void normalize_sol(const Scaling &sc, real *x, real *y, real *s);
 void un_normalize_sol(const Scaling &sc, real *x, real *y, real *s);
 int validate_csc(const ScsMatrix *M, int rows, int cols, bool upper_only, const char *name);

@@ -86,6 +86,21 @@ template <int W, typename T> __device__ __forceinline__ T block_col_max(T v, T *
   return s;
 }
 
+// consumer side of the two-level reduction, per column: `part` holds count x W entries, entry (b, k) at b * W + k
+template <int W> __device__ __forceinline__ real reduce_partials_col_sum(const real *part, int count, real *sh) {
+  real s = 0;
+  for (int i = threadIdx.x; i < count * W; i += SCSAMD_BLOCK) s += part[i]; // SCSAMD_BLOCK % W == 0: a thread stays in its column
+  return block_col_sum<W>(s, sh);
+}
+template <int W> __device__ __forceinline__ real reduce_partials_col_max(const real *part, int count, real *sh) {
+  real s = 0;
+  for (int i = threadIdx.x; i < count * W; i += SCSAMD_BLOCK) {
+    const real v = part[i];
+    s = v > s ? v : s;
+  }
+  return block_col_max<W>(s, sh);
+}
+
 // epilogues of spmv.h on element (r, col) of a block; d (R_x / R_y) is shared by the columns
 template <int EPI, int W>
 __device__ __forceinline__ real epi_init_blk(const EpiArgs &e, const real *y, size_t o) {

@@ -93,6 +93,44 @@ class SCS:
         if self._lib.scs_update(self._w, bp, cp) != 0:
             raise RuntimeError("scs_update failed")
 
+    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None):
+        """scs_amd_solve_family: K problems that share A, P and the cones of this object and differ in (b, c), in one
+        device-resident loop.  B: m x K, C: n x K, as arrays or as lists of K vectors.  With warm_start, x (n x K), y and
+        s (m x K) seed the columns.  Returns a list of K dicts in the shape `solve` returns.  The object's own problem and
+        its last solution are not touched.  Needs adaptive_scale=0, acceleration_lookback=0 and no log_csv_filename:
+        otherwise ValueError with the library's message."""
+        if not self._w:
+            raise RuntimeError("solver was closed")
+        m, n = self._prob.m, self._prob.n
+
+        def block(v, rows, what):
+            if isinstance(v, (list, tuple)):
+                v = np.column_stack([np.asarray(c, dtype=float).reshape(-1) for c in v]) if len(v) else np.zeros((rows, 0))
+            v = np.asarray(v, dtype=float)
+            if v.ndim == 1:
+                v = v.reshape(-1, 1)
+            if v.ndim != 2 or v.shape[0] != rows:
+                raise ValueError(f"{what} must have {rows} rows")
+            return v
+        B, C_ = block(B, m, "B"), block(C, n, "C")
+        K = B.shape[1]
+        if K < 1 or C_.shape[1] != K:
+            raise ValueError("B and C must have the same number K >= 1 of columns")
+        why = self._lib.scs_amd_solve_family_refusal(self._w)
+        if why:
+            raise ValueError(why.decode())
+        warm = None
+        if warm_start:
+            if x is None or y is None or s is None:
+                raise ValueError("warm_start needs x, y and s")
+            warm = (block(x, n, "x"), block(y, m, "y"), block(s, m, "s"))
+            if any(v.shape[1] != K for v in warm):
+                raise ValueError("warm-start blocks must have K columns")
+        rc, out = capi.solve_family(self._lib, self._w, B, C_, warm=warm)
+        if rc != 0:
+            raise RuntimeError("scs_amd_solve_family failed")
+        return out
+
     def close(self):
         if getattr(self, "_w", None):
             self._lib.scs_finish(self._w)
