@@ -238,17 +238,21 @@ __global__ __launch_bounds__(WR_BLOCK) void csr_wave_wide_kernel(WaveView A, con
 // program-order adds as the plain kernel: bit-reproducible.  Variants measured and dropped: 8 waves per workgroup (66.4 us), one barrier per
 // chunk (65.1; kept for matrices whose gathers share lines: 34.0 vs 35.3 us on the band), the next chunk's stream loads issued behind the
 // gathers (67.3) or ahead of them (62.6), an x-window prefetch (73.7), 16 waves as two workgroups (69.7).
-template <int EPI, int WL_WPB, int MODE> // MODE = barriers per chunk (4: in front of every gather instruction | 1)
-__global__ __launch_bounds__(WL_WPB * 64) void csr_wave_lockstep_kernel(WaveView A, const real *__restrict__ x, real *y, EpiArgs e,
-                                                                        const int *skip, int accrows) {
-  if (skip && *skip) return;
-  extern __shared__ __attribute__((aligned(16))) unsigned char wr_smem[];
-  __shared__ real red[3][WL_WPB];
-  __shared__ int s_nch[WL_WPB];
+// Epilogue operands ahead of the chunk loop (EPI_DIV, EPI_GP): the epilogue's reads -- d, and for EPI_GP xin and y0 -- used to be issued by
+// every wave after its last chunk, by all waves of the chip at about the same moment and with nothing left to overlap the HBM round trip
+// with.  A lane now loads the operands of its rows r0 + lane + 64 j, j < SLOTS, into registers right behind the first chunk's stream loads
+// (an HBM miss anyway: the operands cost bandwidth there, no round trip of their own) and the epilogue runs from those registers with
+// epi_apply_pre: the same loads, the same arithmetic in the same order, the same bits.  SLOTS is the smallest of 4 | 9 | 16 that covers
+// accrows (a uniform branch in the kernel: 16 covers WR_ROWS_MAX; EPI_GP, three operands per slot, stops at 9: 16 would spill); a row beyond
+// the slots takes the late loads.  A wave without a unit in a round loads nothing.  108 / 126 VGPRs, no scratch: one workgroup of 16 waves
+// per CU still fits.  Measured: profiles/spmv_epilogue_prefetch.md.
+template <int EPI, int WL_WPB, int MODE, int SLOTS> // MODE = barriers per chunk (4: in front of every gather instruction | 1)
+__device__ __forceinline__ void wave_lockstep_rounds(const WaveView &A, const real *__restrict__ x, real *y, const EpiArgs &e, real *acc,
+                                                     int *s_nch, real &dot, real &d1, real &d2) {
+  constexpr bool PRE = SLOTS > 0 && (EPI == EPI_DIV || EPI == EPI_GP);
+  constexpr int NS = PRE ? SLOTS : 1;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  real *acc = reinterpret_cast<real *>(wr_smem) + (size_t)wave * accrows;
   const unsigned cmask = (1u << A.cbits) - 1;
-  real dot = 0, d1 = 0, d2 = 0;
   const int per_round = gridDim.x * WL_WPB;
   const int nround = (A.nunit + per_round - 1) / per_round;
   for (int rd = 0; rd < nround; ++rd) {
@@ -288,16 +292,77 @@ __global__ __launch_bounds__(WL_WPB * 64) void csr_wave_lockstep_kernel(WaveView
     WrChunk zero;
     zero.w = make_uint4(0, 0, 0, 0);
     zero.v[0] = zero.v[1] = zero.v[2] = zero.v[3] = 0;
-    for (int c = 0; c < nmax; ++c) {
-      const WrChunk ch = c < nch ? wr_load(A, s + c * 256 + lane * 4) : zero;
-      consume(ch, c);
-    }
-    for (int k = lane; k < nr; k += 64) {
-      const real a = epi_init<EPI>(e, y, r0 + k) + acc[k];
-      if (EPI == EPI_GP3) epi_apply3(e, y, r0 + k, a, dot, d1, d2);
-      else epi_apply<EPI>(e, y, r0 + k, a, dot);
+    if (PRE) {
+      // the first chunk's stream loads, then the epilogue operands, then the gathers; all of them in ONE branch, so that the wait in
+      // front of the first gather counts the operand loads behind the stream loads and lets them stay in flight
+      WrChunk ch0 = zero;
+      real pd[NS], px[NS], py[NS];
+      if (live) { // (a unit has at least one row; one without entries reads the padding behind its start: harmless)
+        ch0 = wr_load(A, s + lane * 4);
+        // the unit's first row is the same for the whole wave: scalar bases, one 32-bit offset per slot shared by the three arrays (a lane
+        // whose slot lies behind the unit's last row re-reads the first row and never uses it: no branch per load)
+        const int rb = __builtin_amdgcn_readfirstlane(r0);
+        const real *dp = e.d + rb, *xp = EPI == EPI_GP ? e.xin + rb : nullptr, *yp = EPI == EPI_GP && e.y0 ? e.y0 + rb : nullptr;
+        unsigned ko[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) ko[j] = lane + 64 * j < nr ? (unsigned)(lane + 64 * j) : 0u;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          pd[j] = dp[ko[j]];
+          if (EPI == EPI_GP) px[j] = xp[ko[j]];
+        }
+        if (EPI == EPI_GP && e.y0) {
+#pragma unroll
+          for (int j = 0; j < NS; ++j) py[j] = yp[ko[j]];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NS; ++j) { // what the epilogue does not read: the constants of epi_init / epi_apply_pre
+        if (EPI != EPI_GP) px[j] = 0;
+        if (!(EPI == EPI_GP && e.y0)) py[j] = 0;
+      }
+      if (0 < nmax) consume(ch0, 0);
+      for (int c = 1; c < nmax; ++c) {
+        const WrChunk ch = c < nch ? wr_load(A, s + c * 256 + lane * 4) : zero;
+        consume(ch, c);
+      }
+#pragma unroll
+      for (int j = 0; j < NS; ++j) {
+        const int k = lane + 64 * j;
+        if (k < nr) epi_apply_pre<EPI>(y, r0 + k, py[j] + acc[k], pd[j], px[j], dot);
+      }
+      for (int k = lane + 64 * NS; k < nr; k += 64) epi_apply<EPI>(e, y, r0 + k, epi_init<EPI>(e, y, r0 + k) + acc[k], dot);
+    } else {
+      for (int c = 0; c < nmax; ++c) {
+        const WrChunk ch = c < nch ? wr_load(A, s + c * 256 + lane * 4) : zero;
+        consume(ch, c);
+      }
+      for (int k = lane; k < nr; k += 64) {
+        const real a = epi_init<EPI>(e, y, r0 + k) + acc[k];
+        if (EPI == EPI_GP3) epi_apply3(e, y, r0 + k, a, dot, d1, d2);
+        else epi_apply<EPI>(e, y, r0 + k, a, dot);
+      }
     }
     __syncthreads(); // s_nch is rewritten by the next round
+  }
+}
+template <int EPI, int WL_WPB, int MODE>
+__global__ __launch_bounds__(WL_WPB * 64) void csr_wave_lockstep_kernel(WaveView A, const real *__restrict__ x, real *y, EpiArgs e,
+                                                                        const int *skip, int accrows) {
+  if (skip && *skip) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char wr_smem[];
+  __shared__ real red[3][WL_WPB];
+  __shared__ int s_nch[WL_WPB];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  real *acc = reinterpret_cast<real *>(wr_smem) + (size_t)wave * accrows;
+  real dot = 0, d1 = 0, d2 = 0;
+  if (EPI == EPI_DIV || EPI == EPI_GP) {
+    const int need = (accrows + 63) >> 6; // register slots per lane that cover every row of a unit
+    if (need <= 4) wave_lockstep_rounds<EPI, WL_WPB, MODE, 4>(A, x, y, e, acc, s_nch, dot, d1, d2);
+    else if (need <= 9 || EPI == EPI_GP) wave_lockstep_rounds<EPI, WL_WPB, MODE, 9>(A, x, y, e, acc, s_nch, dot, d1, d2);
+    else wave_lockstep_rounds<EPI, WL_WPB, MODE, 16>(A, x, y, e, acc, s_nch, dot, d1, d2);
+  } else {
+    wave_lockstep_rounds<EPI, WL_WPB, MODE, 0>(A, x, y, e, acc, s_nch, dot, d1, d2);
   }
   if ((EPI == EPI_GP || EPI == EPI_GP3) && e.partial) wr_block_partials<EPI, WL_WPB>(e, red, dot, d1, d2, wave, lane);
 }
