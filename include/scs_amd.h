@@ -481,8 +481,8 @@ scs_int scs_amd_aa_safeguard(scs_float *f_new, scs_float *x_new, void *a);
 void scs_amd_aa_reset(void *a);
 void scs_amd_aa_finish(void *a);
 void scs_amd_aa_get_stats(const void *a, AaStats *out);
-/* Device-resident Anderson acceleration (what scs_solve uses once n+m+1 >= 32768; env
- * SCS_AMD_AA=host|dev forces either): same contract again, replacing aa_init / aa_apply /
+/* Device-resident Anderson acceleration (what scs_solve uses once n+m+1 >= 32768; the option
+ * `aa` = host|dev of scs_amd_set_option forces either): same contract again, replacing aa_init / aa_apply /
  * aa_safeguard / aa_reset / aa_finish of include/aa.h:66-143.  These wrappers take HOST
  * pointers and stage them through HBM so the device path can be pinned against the
  * reference's AA on identical sequences; inside scs_solve the iterates never leave HBM.
@@ -496,6 +496,55 @@ scs_int scs_amd_aa_dev_safeguard(scs_float *f_new, scs_float *x_new, void *a);
 void scs_amd_aa_dev_reset(void *a);
 void scs_amd_aa_dev_finish(void *a);
 void scs_amd_aa_dev_get_stats(const void *a, AaStats *out);
+/* ---- A block of accelerations at once -------------------------------------------------------------------------------------
+ * K = nrhs independent accelerations (1 <= nrhs <= 16) that share their kernels and their read-backs: column k computes what
+ * scs_amd_aa_dev_apply / _safeguard compute for that column alone -- its own iteration count, ring slot, memory length, success
+ * flag, norms and AaStats; nothing couples the columns -- but every kernel of the reflector sweep is enqueued once for all
+ * columns and every host decision of one reflector step is taken from one read-back.  The host synchronisations of one block
+ * apply are at most max_k len_k + 4 whatever K is (scs_amd/csrc/aa_multi.h).  Columns may be in different phases in one call:
+ * seeding after a reset or a rejection, filling their memory, solving with memories of different lengths.
+ * The object has a fixed width W = scs_amd_aa_multi_width(nrhs) in {2, 4, 8, 16} (1 for nrhs == 1, 0 if nrhs < 1 or > 16); there
+ * is no chunking beyond 16 columns.  init arguments as scs_amd_aa_dev_init, shared by the columns; NULL on bad arguments or a
+ * HIP failure.
+ *   Host entries (apply, safeguard): F / X are column-major, nrhs columns of length dim with leading dimension >= dim; rows
+ *     beyond dim are not touched.  They stage the columns through HBM (staging buffers are created at the first such call).
+ *   Device entries (_dev): F_dev / X_dev are device pointers in the block layout of the other block entries, row-major with
+ *     element (i, k) at i * W + k; columns nrhs .. W-1 are neither read nor written.  The caller synchronises its own work before
+ *     the call; the call returns with the object's private stream idle (the algorithm reads scalars back anyway).
+ *   skip: nrhs flags, or NULL.  Nothing of a skipped column is read or written, its state does not move, aa_norm[k] = 0 and
+ *     rejected[k] = 0 (the frozen columns of a family solve).
+ *   aa_norm[k]: what aa_apply returns for column k -- 0 while seeding or filling, negative on a rejected solve, positive when
+ *     the step was applied (F updated in place).
+ *   rejected[k]: 0 or -1, as aa_safeguard returns (-1: F_new / X_new of that column were put back to the last accepted pair and
+ *     the column restarts from an empty memory).  A column whose last apply did not succeed is not tested.
+ *   nrhs == 1 is the single-vector device path, bit for bit (of the counters only out[0] moves then).  For nrhs > 1 the result
+ *     agrees with it to rounding amplified by the least-squares solve, not bit for bit: the sums are ordered differently.  Within
+ *     one width the bits of a column depend neither on the other columns nor on its position, and a run repeats bit for bit.
+ *   Return: 0 on success; -1 on bad arguments (checked before any device call, F untouched); -1 on a HIP failure (message on
+ *     stderr, every column reset, F unspecified, the object stays usable).
+ *   reset: col < 0 resets every column.  get_stats: the AaStats of one column.
+ *   get_counters: out[0] = block applies, out[1] = host synchronisations inside applies, out[2] = host synchronisations inside
+ *     safeguards, out[3] = kernel launches.
+ *   Memory, all allocated at init and freed at finish: per column (3 mem + (type1 ? 2 : 1) mem + 1) vectors of dim (S, D, Y and
+ *     the QR panel) plus five work vectors (x, f, g, g_prev, and x_work when relaxation != 1).  At dim = 3e6, lookback 10, type I
+ *     that is about 1.2 GB per column. */
+typedef struct SCS_AMD_AA_MULTI ScsAmdAaMulti;
+scs_int scs_amd_aa_multi_width(scs_int nrhs);
+ScsAmdAaMulti *scs_amd_aa_multi_init(scs_int dim, scs_int nrhs, scs_int mem, scs_int min_len, scs_int type1,
+                                     scs_float regularization, scs_float relaxation, scs_float safeguard_factor,
+                                     scs_float max_weight_norm, scs_int ir_max_steps);
+scs_int scs_amd_aa_multi_apply(ScsAmdAaMulti *a, scs_float *F, scs_int ldf, const scs_float *X, scs_int ldx,
+                               const scs_int *skip, scs_float *aa_norm);
+scs_int scs_amd_aa_multi_safeguard(ScsAmdAaMulti *a, scs_float *F_new, scs_int ldf, scs_float *X_new, scs_int ldx,
+                                   const scs_int *skip, scs_int *rejected);
+scs_int scs_amd_aa_multi_apply_dev(ScsAmdAaMulti *a, scs_float *F_dev, const scs_float *X_dev,
+                                   const scs_int *skip, scs_float *aa_norm);
+scs_int scs_amd_aa_multi_safeguard_dev(ScsAmdAaMulti *a, scs_float *F_dev, scs_float *X_dev,
+                                       const scs_int *skip, scs_int *rejected);
+void scs_amd_aa_multi_reset(ScsAmdAaMulti *a, scs_int col);
+void scs_amd_aa_multi_get_stats(const ScsAmdAaMulti *a, scs_int col, AaStats *out);
+void scs_amd_aa_multi_get_counters(const ScsAmdAaMulti *a, long long out[4]);
+void scs_amd_aa_multi_finish(ScsAmdAaMulti *a);
 /* ---- ONE linear system split by rows of A across GPUs, native form -------------------------------------------
  * The operator of linsys/cpu/indirect/private.c:106-119 is a sum over row slabs: G = R_x + A' R_y^-1 A = sum_r (R_x / N + A_r' R_r^-1 A_r).
  * Rank r creates a workspace on ITS slab (rows [r0, r1) of A, all n columns, CSC) with diag_r_local = [R_x / N (n) ; R_y of the

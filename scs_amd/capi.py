@@ -209,6 +209,27 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
                                                  C.POINTER(T.ScsInfo), scs_int]
             lib.scs_amd_solve_family_refusal.restype = C.c_char_p
             lib.scs_amd_solve_family_refusal.argtypes = [C.c_void_p]
+            # a block of Anderson accelerations at once (include/scs_amd.h; scs_amd/accel.py is the object form)
+            lib.scs_amd_aa_multi_width.restype = scs_int
+            lib.scs_amd_aa_multi_width.argtypes = [scs_int]
+            lib.scs_amd_aa_multi_init.restype = C.c_void_p
+            lib.scs_amd_aa_multi_init.argtypes = [scs_int] * 5 + [T.ftype] * 4 + [scs_int]
+            lib.scs_amd_aa_multi_apply.restype = scs_int
+            lib.scs_amd_aa_multi_apply.argtypes = [C.c_void_p, fp, scs_int, fp, scs_int, T.ip, fp]
+            lib.scs_amd_aa_multi_safeguard.restype = scs_int
+            lib.scs_amd_aa_multi_safeguard.argtypes = [C.c_void_p, fp, scs_int, fp, scs_int, T.ip, T.ip]
+            lib.scs_amd_aa_multi_apply_dev.restype = scs_int
+            lib.scs_amd_aa_multi_apply_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, T.ip, fp]  # device pointers
+            lib.scs_amd_aa_multi_safeguard_dev.restype = scs_int
+            lib.scs_amd_aa_multi_safeguard_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, T.ip, T.ip]
+            lib.scs_amd_aa_multi_reset.restype = None
+            lib.scs_amd_aa_multi_reset.argtypes = [C.c_void_p, scs_int]
+            lib.scs_amd_aa_multi_get_stats.restype = None
+            lib.scs_amd_aa_multi_get_stats.argtypes = [C.c_void_p, scs_int, C.POINTER(T.AaStats)]
+            lib.scs_amd_aa_multi_get_counters.restype = None
+            lib.scs_amd_aa_multi_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
+            lib.scs_amd_aa_multi_finish.restype = None
+            lib.scs_amd_aa_multi_finish.argtypes = [C.c_void_p]
             # one linear system split by rows across GPUs, native form (scs_amd/csrc/shard_native.cpp)
             lib.scs_amd_shard_unique_id.restype = scs_int
             lib.scs_amd_shard_unique_id.argtypes = [C.c_char_p]

@@ -698,3 +698,5 @@ void scs_amd_aa_dev_finish(void *hv) {
   delete h;
 }
 }
+
+#include "aa_multi.h"
