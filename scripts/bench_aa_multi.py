@@ -10,7 +10,8 @@ run).  Both sides first take lookback + 2 applies (seed, fill, first full solves
 memory are timed one by one, with HIP events on the null stream around the call and with the wall clock; the uploads of the next
 pair of blocks are outside both.  Every apply returns with its stream idle, so the two clocks see the same interval.
 One JSON line per (dim, K): medians, time per column, its ratio to the single-vector apply, host synchronisations and kernel
-launches per apply.  No pass mark: it reports."""
+launches per apply.  --lib-dir measures a library built elsewhere (an A/B against another commit's build, one process per
+library).  No pass mark: it reports."""
 import argparse
 import ctypes as C
 import json
@@ -135,7 +136,10 @@ def main():
     ap.add_argument("--lookback", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--lib", default="libscsamd.so")
+    ap.add_argument("--lib-dir", default=None, help="load --lib from this directory instead of scs_amd/lib (another build of it)")
     a = ap.parse_args()
+    if a.lib_dir:
+        capi.LIB_DIR = os.path.abspath(a.lib_dir)
     lib = capi.load(a.lib)
     if lib.scs_amd_device_count() <= 0:
         sys.exit("bench_aa_multi: no GPU (a measurement path does not fall back)")

@@ -6,6 +6,13 @@
 // blockIdx.y = column and the per-column arguments (pivot, tau, scale, beta, column set) passed by value.  A column that seeds,
 // fills its memory below min_len, is skipped or has run out of reflectors has n == 0 in that launch and returns at once.
 //
+// Where each piece lives.  The host side of a column -- counters, norms, AaStats, pivot choice with norm downdating, reflector
+// scalars, and everything from the top rows of its panel to gamma and the accept / reject decision -- is AaPanelCol of
+// aa_small.h, the same object the single-vector path derives from; for K == 1 the object holds a complete AaDev and runs that
+// path itself.  The four panel passes (build, dots, w, update) are the __device__ bodies of aa_dev.hip behind entry points
+// that pick their column's pointers and arguments out of AamArgs / AamBuild.  This file adds the kernels that touch the block
+// layout, the device-side second reduction level, the lock-step sweep and the C ABI.
+//
 // Layout.  F and X arrive in the block layout of the other block entries (row-major, element (i, k) at i * W + k).  The state of a
 // column -- S, D, Y, x, f, g, g_prev, x_work and its QR panel -- stays contiguous per column exactly as AaDev lays it out, because
 // the sweeps address a different panel column per problem (its pivot, its ring slot).  The kernels that touch F / X (ingest =
@@ -224,153 +231,52 @@ k_aam_restore(real *__restrict__ Fb, real *__restrict__ Xb, int W, int wsh, long
   }
 }
 
-// ---- the panel kernels of aa_dev.hip, one column per blockIdx.y (build: blockIdx.z) --------------------
+// ---- the panel passes of aa_dev.hip, one column per blockIdx.y (build: blockIdx.z): entry points that resolve --------
+// ---- their column's pointers and arguments and run the same bodies ------------------------------------------------
 __global__ void __launch_bounds__(SCSAMD_BLOCK)
 k_aam_build(real *__restrict__ Q, size_t qs, long ld, long dim, long aug, int mem, int type1, AamBuild bd,
             const real *__restrict__ S, const real *__restrict__ Y, size_t ms, const real *__restrict__ g, size_t vs) {
   const int p = blockIdx.z, len = bd.len[p], cy = blockIdx.y;
   if (len == 0 || cy >= len + (type1 ? len : 0) + 1) return;
-  const real *src;
-  int phys, unit;
-  if (cy < len) {
-    src = (type1 ? S : Y) + (size_t)p * ms + (size_t)cy * dim;
-    phys = cy;
-    unit = cy;
-  } else if (type1 && cy < 2 * len) {
-    src = Y + (size_t)p * ms + (size_t)(cy - len) * dim;
-    phys = mem + (cy - len);
-    unit = cy - len;
-  } else {
-    src = g + (size_t)p * vs;
-    phys = type1 ? 2 * mem : mem;
-    unit = -1;
-  }
-  const real sqrt_r = bd.sqrt_r[p];
-  real *dst = Q + (size_t)p * qs + (size_t)phys * ld;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < aug; i += (long)gridDim.x * blockDim.x) {
-    real v;
-    if (i < dim) v = src[i];
-    else v = (unit >= 0 && i - dim == unit) ? sqrt_r : (real)0;
-    dst[i] = v;
-  }
+  aa_build_body(Q + (size_t)p * qs, ld, dim, aug, mem, len, type1, cy, (type1 ? S : Y) + (size_t)p * ms, Y + (size_t)p * ms,
+                g + (size_t)p * vs, bd.sqrt_r[p]);
 }
 
 // part[p][c][wg] = sum_{i >= lo} Q_p[piv][i] * Q_p[col_c][i]
 __global__ void __launch_bounds__(SCSAMD_BLOCK)
 k_aam_dots(const real *__restrict__ Qall, size_t qs, long ld, long aug, long lo, AamArgs a, real *__restrict__ part,
            size_t ps) {
-  __shared__ real sh[SCSAMD_BLOCK / 64][AA_BATCH];
   const int p = blockIdx.y, n = a.c[p].n;
   if (n == 0 || !a.c[p].apply) return;
-  const real *Q = Qall + (size_t)p * qs;
-  real acc[AA_BATCH];
-  int col[AA_BATCH];
+  int col[AA_BATCH]; // out of the kernarg once (its offset depends on p), not once per row
 #pragma unroll
-  for (int c = 0; c < AA_BATCH; ++c) {
-    acc[c] = 0;
-    col[c] = a.c[p].col[c];
-  }
-  const real *vp = Q + (size_t)a.c[p].piv * ld;
-  for (long i = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i < aug; i += (long)gridDim.x * blockDim.x) {
-    const real v = vp[i];
-#pragma unroll
-    for (int c = 0; c < AA_BATCH; ++c)
-      if (c < n) acc[c] += v * Q[(size_t)col[c] * ld + i];
-  }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < AA_BATCH; ++c) {
-    if (c < n) {
-      const real s = wave_sum(acc[c]);
-      if (l == 0) sh[w][c] = s;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < n) {
-    real s = sh[0][threadIdx.x];
-    for (int k = 1; k < SCSAMD_BLOCK / 64; ++k) s += sh[k][threadIdx.x];
-    part[(size_t)p * ps + (size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-  }
+  for (int c = 0; c < AA_BATCH; ++c) col[c] = a.c[p].col[c];
+  qr_dots_body(Qall + (size_t)p * qs, ld, aug, lo, a.c[p].piv, n, col, part + (size_t)p * ps);
 }
 
-// one workgroup per column: w_c = tau (Q[col_c][k] + vscale * dot_c); Q[col_c][k] -= w_c; R_kk = beta into the pivot column
+// one workgroup per column; small[p]: w | row-k entry
 __global__ void __launch_bounds__(SCSAMD_BLOCK)
 k_aam_w(real *__restrict__ Qall, size_t qs, long ld, long k, AamArgs a, const real *__restrict__ part, size_t ps, int nparts,
         real *__restrict__ small, size_t ss) {
   const int p = blockIdx.y, n = a.c[p].n;
   if (n == 0 || !a.c[p].apply) return;
-  real *Q = Qall + (size_t)p * qs;
-  const real *pp = part + (size_t)p * ps;
   real *sm = small + (size_t)p * ss;
-  const real tau = a.c[p].tau, vscale = a.c[p].vscale;
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  for (int c = w; c < n; c += SCSAMD_BLOCK / 64) {
-    real s = 0;
-    for (int i = l; i < nparts; i += 64) s += pp[(size_t)c * nparts + i];
-    s = wave_sum(s);
-    if (l == 0) {
-      real *e = Q + (size_t)a.c[p].col[c] * ld + k;
-      const real ck = *e;
-      const real wc = tau * (ck + vscale * s);
-      *e = ck - wc;
-      sm[c] = wc;
-      sm[AA_BATCH + c] = ck - wc;
-    }
-  }
-  if (a.c[p].set_beta && threadIdx.x == 0) Q[(size_t)a.c[p].piv * ld + k] = a.c[p].beta;
+  qr_w_body(Qall + (size_t)p * qs, ld, k, a.c[p].piv, a.c[p].tau, a.c[p].vscale, a.c[p].beta, a.c[p].set_beta, n, a.c[p].col,
+            part + (size_t)p * ps, nparts, sm, sm + AA_BATCH);
 }
 
-// rows i >= lo of every column in the set: x -= w_c * vscale * Q[piv][i] (if apply); statistics for the next pivot step:
-// small[2 AA_BATCH + c] = x at row lo, part_ss[p][c][wg] = sum of squares over rows > lo
+// small[p][2 AA_BATCH + c] = x at row lo, part_ss[p][c][wg] = sum of squares over rows > lo
 __global__ void __launch_bounds__(SCSAMD_BLOCK)
 k_aam_update(real *__restrict__ Qall, size_t qs, long ld, long aug, long lo, AamArgs a, real *__restrict__ part_ss, size_t ps,
              real *__restrict__ small, size_t ss) {
-  __shared__ real sh[SCSAMD_BLOCK / 64][AA_BATCH];
   const int p = blockIdx.y, n = a.c[p].n;
   if (n == 0) return;
-  real *Q = Qall + (size_t)p * qs;
   real *sm = small + (size_t)p * ss;
-  const int do_update = a.c[p].apply;
-  const real vscale = a.c[p].vscale;
-  real sq[AA_BATCH], wv[AA_BATCH];
   int col[AA_BATCH];
 #pragma unroll
-  for (int c = 0; c < AA_BATCH; ++c) {
-    sq[c] = 0;
-    wv[c] = (do_update && c < n) ? sm[c] : (real)0;
-    col[c] = a.c[p].col[c];
-  }
-  const real *vp = Q + (size_t)a.c[p].piv * ld;
-  for (long i = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i < aug; i += (long)gridDim.x * blockDim.x) {
-    const real v = do_update ? vscale * vp[i] : (real)0;
-#pragma unroll
-    for (int c = 0; c < AA_BATCH; ++c) {
-      if (c < n) {
-        real *e = Q + (size_t)col[c] * ld + i;
-        real x = *e;
-        if (do_update) {
-          x -= wv[c] * v;
-          *e = x;
-        }
-        if (i > lo) sq[c] += x * x;
-        else sm[2 * AA_BATCH + c] = x;
-      }
-    }
-  }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-#pragma unroll
-  for (int c = 0; c < AA_BATCH; ++c) {
-    if (c < n) {
-      const real s = wave_sum(sq[c]);
-      if (l == 0) sh[w][c] = s;
-    }
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < n) {
-    real s = sh[0][threadIdx.x];
-    for (int k = 1; k < SCSAMD_BLOCK / 64; ++k) s += sh[k][threadIdx.x];
-    part_ss[(size_t)p * ps + (size_t)threadIdx.x * gridDim.x + blockIdx.x] = s;
-  }
+  for (int c = 0; c < AA_BATCH; ++c) col[c] = a.c[p].col[c];
+  qr_update_body(Qall + (size_t)p * qs, ld, aug, lo, a.c[p].piv, a.c[p].vscale, a.c[p].apply, n, col, sm, part_ss + (size_t)p * ps,
+                 sm + 2 * AA_BATCH);
 }
 
 // second level of every reduction: one wave per value.  Value e (group q = e / grp, member c = e % grp) is the sum of the G
@@ -411,9 +317,10 @@ struct AaMulti {
   hipStream_t st = nullptr;
   int G = 1, gt = 1, gd = 1; // grids: panel passes, tile kernels, the safeguard's difference
   size_t vs = 0, ms = 0, qs = 0;
-  // K == 1: col[0] is a complete AaDev on `st` (the single-vector path itself).  K > 1: col[k] carries the host side of
-  // column k only (counters, norms, pivoting state, AaStats); the device side is below, column k at k * stride.
-  std::vector<AaDev *> col;
+  // K == 1: col[0] is a complete AaDev on `st` (the single-vector path itself).  K > 1: col[k] is the host side of column k
+  // (aa_small.h); the device side is below, column k at k * stride.
+  std::vector<AaPanelCol *> col;
+  AaDev *one() const { return static_cast<AaDev *>(col[0]); }
   DevBuf<real> x, f, g, g_prev, x_work, Y, S, D, Q;
   DevBuf<real> part;  // [K][2 MB][AA_BATCH][G] dot partials, then sum-of-squares partials; reused as [KMAX][3][gt] and [KMAX][gd]
   DevBuf<real> small; // [K][MB][AAM_SMALL]
@@ -444,35 +351,12 @@ static void aam_sync(AaMulti *m) {
   m->idle = true;
 }
 
-static AaDev *aam_host_col(const AaMulti *m, int min_len, real regularization, real safeguard_factor, real max_weight_norm,
-                           int ir_max_steps) {
-  AaDev *a = new AaDev();
-  const size_t mm = (size_t)m->mem;
-  a->type1 = m->type1;
-  a->dim = m->dim;
-  a->mem = m->mem;
-  a->min_len = std::min(min_len, m->mem);
-  a->regularization = regularization;
-  a->relaxation = m->relaxation;
-  a->safeguard_factor = safeguard_factor;
-  a->max_weight_norm = max_weight_norm;
-  a->ir_max_steps = ir_max_steps;
-  memset(&a->stt, 0, sizeof a->stt);
-  a->stt.last_aa_norm = (real)NAN;
-  a->nrm_s_col.assign(mm, 0); a->nrm_y_col.assign(mm, 0);
-  a->cn.assign(mm, 0); a->cn0.assign(mm, 0); a->tau.assign(mm, 0);
-  a->E.assign(m->ncols, 0); a->SS.assign(m->ncols, 0); a->CK.assign(m->ncols, 0);
-  a->top.assign((size_t)m->ncols * mm, 0); a->Rm.assign(mm * mm, 0);
-  a->W.assign(mm * mm, 0); a->W_orig.assign(mm * mm, 0);
-  a->gamma.assign(mm, 0); a->gamma_red.assign(mm, 0); a->c_top.assign(mm, 0); a->ir_res.assign(mm, 0);
-  a->jpvt.assign(mm, 0); a->ipiv.assign(mm, 0);
-  return a;
-}
-
 void aa_multi_finish(AaMulti *m) {
   if (!m) return;
   if (m->st) (void)hipStreamSynchronize(m->st);
-  for (AaDev *a : m->col) aa_dev_finish(a);
+  if (m->K == 1 && !m->col.empty()) aa_dev_finish(m->one());
+  else
+    for (AaPanelCol *a : m->col) delete a;
   hipStream_t st = m->st;
   delete m;
   if (st) (void)hipStreamDestroy(st);
@@ -482,11 +366,8 @@ AaMulti *aa_multi_init(int dim, int nrhs, int mem, int min_len, int type1, real 
                        real safeguard_factor, real max_weight_norm, int ir_max_steps) {
   const int W = aa_multi_width(nrhs);
   const int memc = std::min(mem, dim);
-  if (W == 0 || dim <= 0 || mem < 0 || !std::isfinite((double)regularization) || relaxation < 0 || relaxation > 2 ||
-      safeguard_factor < 0 || max_weight_norm <= 0 || ir_max_steps < 0 || (memc > 0 && min_len < 1)) {
-    printf("Invalid AA parameters.\n");
+  if (W == 0 || !aa_params_ok(dim, mem, min_len, regularization, relaxation, safeguard_factor, max_weight_norm, ir_max_steps))
     return nullptr;
-  }
   AaMulti *m = new AaMulti();
   try {
     HIP_CHECK(hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking));
@@ -504,9 +385,12 @@ AaMulti *aa_multi_init(int dim, int nrhs, int mem, int min_len, int type1, real 
       m->col.push_back(a);
       return m;
     }
-    m->ncols = (type1 ? 2 : 1) * memc + 1;
-    for (int k = 0; k < nrhs; ++k)
-      m->col.push_back(aam_host_col(m, min_len, regularization, safeguard_factor, max_weight_norm, ir_max_steps));
+    for (int k = 0; k < nrhs; ++k) {
+      m->col.push_back(new AaPanelCol());
+      m->col[k]->init(dim, mem, min_len, type1, regularization, relaxation, safeguard_factor, max_weight_norm, ir_max_steps);
+      m->col[k]->init_panel();
+    }
+    m->ncols = m->col[0]->ncols();
     m->step.resize(nrhs);
     if (memc <= 0) return m;
     const size_t K = (size_t)nrhs, d = (size_t)dim, mm = (size_t)memc;
@@ -596,7 +480,7 @@ static void aam_sweep(AaMulti *m, long k) {
   for (int p = 0; p < K; ++p) {
     const AamStep &s = m->step[p];
     if (!s.on) continue;
-    AaDev *a = m->col[p];
+    AaPanelCol *a = m->col[p];
     for (int i = 0; i < s.n_stat; ++i) {
       const int b = i / AA_BATCH, c = i % AA_BATCH, col = s.cols[i];
       const real *sm = m->h.p + (size_t)p * ss + (size_t)b * AAM_SMALL;
@@ -608,91 +492,6 @@ static void aam_sweep(AaMulti *m, long k) {
   }
 }
 
-// The O(mem^2) end of one column's solve, from the top rows of its panel (a->top) to gamma: rank truncation, the small solve
-// with iterative refinement, the weight cap and the rejection bookkeeping -- the host part of aa_dev_solve (aa.c:505-655),
-// restated because that function ends in its own launch.  Returns aa_norm as aa_dev_solve does; a->success says whether
-// a->gamma is to be applied.
-static real aam_small_solve(AaDev *a, int len, real r) {
-  const int mem = a->mem;
-  auto topv = [&](int col, int row) -> real { return a->top[(size_t)col * mem + row]; };
-  int rank = 0, info = 0;
-  {
-    const real r11 = std::fabs(topv(a->jpvt[0], 0));
-    if (r11 > 0) {
-      const real tol = r11 * (real)len * (real)(sizeof(real) == 8 ? DBL_EPSILON : FLT_EPSILON);
-      for (rank = 0; rank < len; ++rank)
-        if (std::fabs(topv(a->jpvt[rank], rank)) < tol) break;
-    }
-    if (rank == 0) info = 1;
-  }
-  if (info == 0) {
-    for (int i = 0; i < rank; ++i) a->c_top[i] = topv(a->col_c(), i);
-    if (a->type1) {
-      for (int i = 0; i < rank; ++i)
-        for (int rr = 0; rr < rank; ++rr) {
-          a->W[(size_t)i * mem + rr] = topv(mem + a->jpvt[i], rr);
-          a->W_orig[(size_t)i * mem + rr] = a->W[(size_t)i * mem + rr];
-        }
-      memcpy(a->gamma_red.data(), a->c_top.data(), rank * sizeof(real));
-      info = lu_factor(a->W.data(), rank, mem, a->ipiv.data());
-      if (info == 0) {
-        lu_solve(a->W.data(), rank, mem, a->ipiv.data(), a->gamma_red.data());
-        real prev = 0;
-        for (int k = 0; k < a->ir_max_steps; ++k) { // aa.c:530-552
-          for (int i = 0; i < rank; ++i) {
-            real s = a->c_top[i];
-            for (int j = 0; j < rank; ++j) s -= a->W_orig[i + (size_t)j * mem] * a->gamma_red[j];
-            a->ir_res[i] = s;
-          }
-          lu_solve(a->W.data(), rank, mem, a->ipiv.data(), a->ir_res.data());
-          const real dn = nrm2(a->ir_res.data(), rank);
-          for (int i = 0; i < rank; ++i) a->gamma_red[i] += a->ir_res[i];
-          if (k > 0 && dn >= (real)0.5 * prev) break;
-          prev = dn;
-        }
-      }
-    } else {
-      for (int j = 0; j < rank; ++j)
-        for (int i = 0; i <= j; ++i) a->Rm[i + (size_t)j * mem] = topv(a->jpvt[j], i);
-      memcpy(a->gamma_red.data(), a->c_top.data(), rank * sizeof(real));
-      upper_solve(a->Rm.data(), mem, rank, a->gamma_red.data());
-      real prev = 0;
-      for (int k = 0; k < a->ir_max_steps; ++k) { // aa.c:566-585
-        for (int i = 0; i < rank; ++i) {
-          real s = 0;
-          for (int j = i; j < rank; ++j) s += a->Rm[i + (size_t)j * mem] * a->gamma_red[j];
-          a->ir_res[i] = a->c_top[i] - s;
-        }
-        upper_solve(a->Rm.data(), mem, rank, a->ir_res.data());
-        const real dn = nrm2(a->ir_res.data(), rank);
-        for (int i = 0; i < rank; ++i) a->gamma_red[i] += a->ir_res[i];
-        if (k > 0 && dn >= (real)0.5 * prev) break;
-        prev = dn;
-      }
-    }
-    if (info == 0) {
-      for (int i = 0; i < len; ++i) a->gamma[i] = 0;
-      for (int i = 0; i < rank; ++i) a->gamma[a->jpvt[i]] = a->gamma_red[i];
-    }
-  }
-  real aa_norm = info == 0 ? nrm2(a->gamma.data(), len) : (real)-1.0;
-  a->stt.last_rank = rank;
-  a->stt.last_regularization = r;
-  a->stt.last_aa_norm = (info == 0 && std::isfinite((double)aa_norm)) ? aa_norm : (real)NAN;
-  if (info != 0 || !std::isfinite((double)aa_norm) || aa_norm >= a->max_weight_norm) {
-    if (rank == 0) a->stt.n_reject_rank0++;
-    else if (info != 0) a->stt.n_reject_lapack++;
-    else if (!std::isfinite((double)aa_norm)) a->stt.n_reject_nonfinite++;
-    else a->stt.n_reject_weight_cap++;
-    a->success = 0;
-    aa_dev_reset(a);
-    if (!std::isfinite((double)aa_norm)) aa_norm = -1.0;
-    return aa_norm < 0 ? aa_norm : -aa_norm;
-  }
-  a->success = 1;
-  return aa_norm;
-}
-
 // solve (aa.c:422-655) of every column with len[p] > 0, in lock step; aa_norm[p] as aa_dev_solve returns it
 static void aam_solve(AaMulti *m, real *Fb, const int *len, real *aa_norm) {
   const int K = m->K, mem = m->mem;
@@ -702,17 +501,7 @@ static void aam_solve(AaMulti *m, real *Fb, const int *len, real *aa_norm) {
   int maxlen = 0;
   for (int p = 0; p < K; ++p) {
     if (len[p] <= 0) continue;
-    AaDev *a = m->col[p];
-    real r;
-    if (a->regularization > 0) {
-      const real ny = frob_from_cols(a->nrm_y_col);
-      const real na = a->type1 ? frob_from_cols(a->nrm_s_col) : ny;
-      r = a->regularization * na * ny;
-    } else if (a->regularization < 0) {
-      r = -a->regularization;
-    } else {
-      r = 0;
-    }
+    const real r = m->col[p]->regularization_r();
     reg[p] = r;
     bd.len[p] = len[p];
     bd.sqrt_r[p] = r > 0 ? std::sqrt(r) : (real)0;
@@ -730,70 +519,30 @@ static void aam_solve(AaMulti *m, real *Fb, const int *len, real *aa_norm) {
     s.n_stat = len[p];
   }
   aam_sweep(m, -1);
-  for (int p = 0; p < K; ++p) {
-    AaDev *a = m->col[p];
-    for (int j = 0; j < len[p]; ++j) {
-      a->jpvt[j] = j;
-      a->cn[j] = a->cn0[j] = std::sqrt(a->E[j] * a->E[j] + a->SS[j]);
-    }
-  }
-  const real tol3z = std::sqrt((real)(sizeof(real) == 8 ? DBL_EPSILON : FLT_EPSILON));
+  for (int p = 0; p < K; ++p) m->col[p]->pivot_begin(len[p]);
   for (int k = 0; k < maxlen; ++k) {
     for (int p = 0; p < K; ++p) {
       AamStep &s = m->step[p];
       s.on = len[p] > k;
       if (!s.on) continue;
-      AaDev *a = m->col[p];
+      AaPanelCol *a = m->col[p];
       const int ln = len[p];
-      int piv = k;
-      for (int j = k + 1; j < ln; ++j)
-        if (a->cn[j] > a->cn[piv]) piv = j;
-      if (piv != k) {
-        std::swap(a->jpvt[k], a->jpvt[piv]);
-        a->cn[piv] = a->cn[k];
-        a->cn0[piv] = a->cn0[k];
-      }
-      const int P = a->jpvt[k];
-      const real alpha = a->E[P], xnorm = std::sqrt(a->SS[P]);
-      real beta = alpha, sc = 0;
-      if (xnorm == 0) {
-        a->tau[k] = 0;
-      } else {
-        beta = -std::copysign(std::hypot(alpha, xnorm), alpha);
-        a->tau[k] = (beta - alpha) / beta;
-        sc = (real)1 / (alpha - beta);
-      }
+      const Reflector h = a->pivot_step(k, ln);
       s.cols.clear();
       for (int j = k + 1; j < ln; ++j) s.cols.push_back(a->jpvt[j]);
       s.n_stat = (int)s.cols.size();
       if (a->type1) // carried (never pivoted) columns: B then c
         for (int j = 0; j < ln; ++j) s.cols.push_back(mem + j);
       s.cols.push_back(a->col_c());
-      s.piv = P;
-      s.apply = a->tau[k] != 0;
-      s.tau = a->tau[k];
-      s.vscale = sc;
-      s.beta = beta;
+      s.piv = a->jpvt[k];
+      s.apply = h.tau != 0;
+      s.tau = h.tau;
+      s.vscale = h.scale;
+      s.beta = h.beta;
     }
     aam_sweep(m, k);
-    for (int p = 0; p < K; ++p) {
-      if (len[p] <= k) continue;
-      AaDev *a = m->col[p];
-      for (int j = k + 1; j < len[p]; ++j) { // norm downdating, as dgeqp3 / aa_host.cpp
-        const int col = a->jpvt[j];
-        if (a->cn[j] != 0) {
-          real t = std::fabs(a->CK[col]) / a->cn[j];
-          t = std::max((real)0, (1 + t) * (1 - t));
-          const real t2 = t * (a->cn[j] / a->cn0[j]) * (a->cn[j] / a->cn0[j]);
-          if (t2 <= tol3z) {
-            a->cn[j] = std::sqrt(a->E[col] * a->E[col] + a->SS[col]);
-            a->cn0[j] = a->cn[j];
-          } else {
-            a->cn[j] *= std::sqrt(t);
-          }
-        }
-      }
-    }
+    for (int p = 0; p < K; ++p)
+      if (len[p] > k) m->col[p]->pivot_downdate(k, len[p]);
   }
   // top rows of every panel column: R, W = top of Q'[Y_piv; ..], c_top
   const size_t tsz = (size_t)m->ncols * mem;
@@ -805,11 +554,12 @@ static void aam_solve(AaMulti *m, real *Fb, const int *len, real *aa_norm) {
   memset(&sel, 0, sizeof sel);
   for (int p = 0; p < K; ++p) {
     if (len[p] <= 0) continue;
-    AaDev *a = m->col[p];
+    AaPanelCol *a = m->col[p];
     for (int c = 0; c < m->ncols; ++c)
       for (int rr = 0; rr < len[p]; ++rr) a->top[(size_t)c * mem + rr] = m->h.p[(size_t)p * tsz + (size_t)c * mem + rr];
-    aa_norm[p] = aam_small_solve(a, len[p], reg[p]);
-    if (a->success) {
+    aa_norm[p] = a->solve_from_top(len[p], reg[p]);
+    if (aa_norm[p] >= 0) {
+      a->success = 1;
       sel.m1 |= 1u << p;
       sel.v[p] = len[p];
       memcpy(m->hg.p + (size_t)p * mem, a->gamma.data(), (size_t)len[p] * sizeof(real));
@@ -833,7 +583,7 @@ static void aam_apply(AaMulti *m, real *Fb, const real *Xb, const int *skip, rea
   memset(&sel, 0, sizeof sel);
   for (int p = 0; p < K; ++p) {
     if (skip[p]) continue;
-    AaDev *a = m->col[p];
+    AaPanelCol *a = m->col[p];
     a->success = 0;
     if (a->iter == 0) {
       sel.m0 |= 1u << p;
@@ -857,7 +607,7 @@ static void aam_apply(AaMulti *m, real *Fb, const real *Xb, const int *skip, rea
     aam_sync(m);
     for (int p = 0; p < K; ++p) {
       if (!((sel.m1 >> p) & 1u)) continue;
-      AaDev *a = m->col[p];
+      AaPanelCol *a = m->col[p];
       const int idx = sel.v[p];
       a->nrm_s_col[idx] = std::sqrt(m->h.p[3 * p]);
       a->nrm_y_col[idx] = std::sqrt(m->h.p[3 * p + 1]);
@@ -871,8 +621,8 @@ static void aam_apply(AaMulti *m, real *Fb, const real *Xb, const int *skip, rea
   if (any_solve) aam_solve(m, Fb, len.data(), aa_norm);
   for (int p = 0; p < K; ++p) {
     if (skip[p]) continue;
-    AaDev *a = m->col[p];
-    if (aa_norm[p] > 0) a->stt.n_accept++;
+    AaPanelCol *a = m->col[p];
+    if (aa_norm[p] > 0) a->st.n_accept++;
     a->iter++;
   }
   if (!m->idle) aam_sync(m); // also: the gamma upload has been consumed
@@ -885,7 +635,7 @@ static void aam_safeguard(AaMulti *m, real *Fb, real *Xb, const int *skip, int *
   unsigned test = 0, rej = 0;
   for (int p = 0; p < K; ++p) {
     rejected[p] = 0;
-    AaDev *a = m->col[p];
+    AaPanelCol *a = m->col[p];
     if (skip[p] || m->mem <= 0 || !a->success) continue;
     a->success = 0;
     test |= 1u << p;
@@ -899,13 +649,13 @@ static void aam_safeguard(AaMulti *m, real *Fb, real *Xb, const int *skip, int *
   aam_sync(m);
   for (int p = 0; p < K; ++p) {
     if (!((test >> p) & 1u)) continue;
-    AaDev *a = m->col[p];
+    AaPanelCol *a = m->col[p];
     const real nd = std::sqrt(m->h.p[p]);
     if (nd > a->safeguard_factor * a->norm_g) {
       rej |= 1u << p;
       rejected[p] = -1;
-      a->stt.n_safeguard_reject++;
-      aa_dev_reset(a);
+      a->st.n_safeguard_reject++;
+      a->reset();
     }
   }
   if (!rej) return;
@@ -927,7 +677,7 @@ void aam_fail(AaMulti *m, const std::exception &e) {
   fprintf(stderr, "%s\n", e.what());
   (void)hipStreamSynchronize(m->st);
   m->idle = true;
-  for (AaDev *a : m->col) aa_dev_reset(a);
+  for (AaPanelCol *a : m->col) a->reset();
 }
 void aam_flags(const AaMulti *m, const scs_int *skip, int *out) {
   for (int p = 0; p < m->K; ++p) out[p] = (skip && skip[p]) ? 1 : 0;
@@ -935,11 +685,11 @@ void aam_flags(const AaMulti *m, const scs_int *skip, int *out) {
 // the single-vector path itself, on the object's stream
 void aam_apply_one(AaMulti *m, real *F_dev, const real *X_dev, const int *sk, scs_float *aa_norm) {
   m->cnt[0]++;
-  aa_norm[0] = sk[0] ? (scs_float)0 : aa_dev_apply(F_dev, X_dev, m->col[0]);
+  aa_norm[0] = sk[0] ? (scs_float)0 : aa_dev_apply(F_dev, X_dev, m->one());
   HIP_CHECK(hipStreamSynchronize(m->st));
 }
 void aam_safeguard_one(AaMulti *m, real *F_dev, real *X_dev, const int *sk, scs_int *rejected) {
-  rejected[0] = sk[0] ? 0 : (scs_int)aa_dev_safeguard(F_dev, X_dev, m->col[0]);
+  rejected[0] = sk[0] ? 0 : (scs_int)aa_dev_safeguard(F_dev, X_dev, m->one());
   HIP_CHECK(hipStreamSynchronize(m->st));
 }
 void aam_stage(AaMulti *m) {
@@ -1090,11 +840,11 @@ scs_int scs_amd_aa_multi_safeguard(ScsAmdAaMulti *a, scs_float *F_new, scs_int l
 void scs_amd_aa_multi_reset(ScsAmdAaMulti *a, scs_int col) {
   if (!a || !a->m) return;
   for (int p = 0; p < a->m->K; ++p)
-    if (col < 0 || col == p) aa_dev_reset(a->m->col[p]);
+    if (col < 0 || col == p) a->m->col[p]->reset();
 }
 void scs_amd_aa_multi_get_stats(const ScsAmdAaMulti *a, scs_int col, AaStats *out) {
   if (!a || !a->m || !out || col < 0 || col >= a->m->K) return;
-  aa_dev_stats(a->m->col[col], out);
+  a->m->col[col]->stats(out);
 }
 void scs_amd_aa_multi_get_counters(const ScsAmdAaMulti *a, long long out[4]) {
   if (!a || !a->m || !out) return;

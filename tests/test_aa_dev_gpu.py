@@ -4,6 +4,7 @@ The device path reorders the O(dim) sums, so agreement is to rounding amplified 
 (regularised) least-squares solve: 1e-6 relative on the iterates, identical accept /
 reject and safeguard decisions."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -26,6 +27,7 @@ def _amd():
         getattr(amd, pre + "safeguard").argtypes = [dp, dp, C.c_void_p]
         getattr(amd, pre + "finish").argtypes = [C.c_void_p]
         getattr(amd, pre + "reset").argtypes = [C.c_void_p]
+        getattr(amd, pre + "get_stats").argtypes = [C.c_void_p, C.POINTER(capi.T64.AaStats)]
     return amd
 
 
@@ -38,6 +40,8 @@ def _ref():
     ref.aa_safeguard.restype = C.c_int
     ref.aa_safeguard.argtypes = [dp, dp, C.c_void_p]
     ref.aa_finish.argtypes = [C.c_void_p]
+    ref.aa_get_stats.restype = capi.T64.AaStats  # returned by value; scs_int = int, scs_float = double in oracle/_ref
+    ref.aa_get_stats.argtypes = [C.c_void_p]
     return ref
 
 
@@ -54,10 +58,11 @@ def _map(dim, seed):
     return lambda v: d0 * v + d1 * np.roll(v, 1) + c + 0.03 * np.maximum(v, 0)
 
 
-def _run(init, apply, safeguard, finish, extra, F, dim, mem, type1, reg, relax, iters=50):
-    a = init(dim, mem, mem, type1, reg, relax, 1.0, 1e10, 5, *extra)
+def _run(init, apply, safeguard, finish, extra, F, dim, mem, type1, reg, relax, iters=50, max_weight=1e10, x0=None,
+         before_finish=None):
+    a = init(dim, mem, mem, type1, reg, relax, 1.0, max_weight, 5, *extra)
     assert a
-    x = np.zeros(dim)
+    x = np.zeros(dim) if x0 is None else x0.copy()
     x_prev = x.copy()
     norms, traj = [], []
     for i in range(iters):
@@ -67,6 +72,8 @@ def _run(init, apply, safeguard, finish, extra, F, dim, mem, type1, reg, relax, 
         x = F(x)
         rej = safeguard(_p(x), _p(x_prev), a)
         traj.append((rej, x.copy()))
+    if before_finish:
+        before_finish(a)
     finish(a)
     return norms, traj
 
@@ -127,3 +134,81 @@ def test_device_aa_reset_and_rejects_bad_parameters():
     assert amd.scs_amd_aa_dev_apply(_p(x1), _p(xp), a) == 0.0   # first call after a reset only seeds
     np.testing.assert_array_equal(x1, keep)
     amd.scs_amd_aa_dev_finish(a)
+
+
+# ---- rejected and degenerate solves --------------------------------------------------------------------------------
+# Two settings under which src/aa.c rejects (or, for the identity under B, neither accepts nor rejects) every solve:
+# the weight cap of 0.5 on a contraction, a rank-0 panel or gamma == 0 on the identity.  No step ever changes f, so
+# the iterates are those of the plain iteration; what is compared is the bookkeeping: the counters against the
+# reference's aa_get_stats, the signs of aa_norm, the safeguard decisions.  tests/test_aa_host.py runs the same
+# cases through the host path and tests/test_aa_multi_gpu.py as columns of one block.
+REJ_DIM, REJ_ITERS, REJ_CAP = 300, 50, 0.5
+REJ_SETTINGS = {"A": (0, 1e-12, 5), "B": (1, -1e-6, 4)}  # type1, regularization, mem (= min_len)
+REJ_MAPS = {"contraction100": 100, "identity": 500, "contraction101": 101}  # map -> seed of the start vector
+COUNTERS = ("iter", "n_accept", "n_reject_lapack", "n_reject_rank0", "n_reject_nonfinite", "n_reject_weight_cap",
+            "n_safeguard_reject", "last_rank")
+
+
+def rej_map(name):
+    return (lambda v: v.copy()) if name == "identity" else _map(REJ_DIM, REJ_MAPS[name])
+
+
+def rej_start(name):
+    return np.random.default_rng(REJ_MAPS[name]).standard_normal(REJ_DIM)
+
+
+def counters(st):
+    return tuple(getattr(st, k) for k in COUNTERS)
+
+
+@functools.lru_cache(maxsize=None)
+def rej_plain(name):
+    """the iterates of x <- F(x), what every side has to reproduce bit for bit"""
+    F, x, out = rej_map(name), rej_start(name), []
+    for _ in range(REJ_ITERS):
+        x = F(x)
+        out.append(x.copy())
+    return out
+
+
+def rej_run(init, apply, safeguard, finish, extra, get_stats, setting, name):
+    """(signs of aa_norm, safeguard decisions, iterates, counters) of one (setting, map) pair"""
+    type1, reg, mem = REJ_SETTINGS[setting]
+    got = {}
+    norms, traj = _run(init, apply, safeguard, finish, extra, rej_map(name), REJ_DIM, mem, type1, reg, 1.0, iters=REJ_ITERS,
+                       max_weight=REJ_CAP, x0=rej_start(name), before_finish=lambda a: got.update(st=counters(get_stats(a))))
+    return np.sign(norms), [t[0] for t in traj], [t[1] for t in traj], got["st"]
+
+
+@functools.lru_cache(maxsize=None)
+def rej_reference(setting, name):
+    ref = _ref()
+    return rej_run(ref.aa_init, ref.aa_apply, ref.aa_safeguard, ref.aa_finish, (0,), ref.aa_get_stats, setting, name)
+
+
+def rej_check(got, setting, name):
+    signs, rejs, traj, st = got
+    rsigns, rrejs, _, rst = rej_reference(setting, name)
+    print(f"setting {setting}, {name}: counters {st}, reference {rst}")
+    assert st == rst
+    assert np.array_equal(signs, rsigns)
+    assert rejs == rrejs
+    for x, want in zip(traj, rej_plain(name)):
+        assert np.array_equal(x.view(np.uint64), want.view(np.uint64))
+
+
+def amd_stats(get_stats):
+    def f(a):
+        st = capi.T64.AaStats()
+        get_stats(a, C.byref(st))
+        return st
+    return f
+
+
+@pytest.mark.skipif(not pyoracle.ref_available(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("name", list(REJ_MAPS))
+@pytest.mark.parametrize("setting", list(REJ_SETTINGS))
+def test_device_aa_rejected_and_degenerate_solves_match_reference(setting, name):
+    amd = _amd()
+    rej_check(rej_run(amd.scs_amd_aa_dev_init, amd.scs_amd_aa_dev_apply, amd.scs_amd_aa_dev_safeguard,
+                      amd.scs_amd_aa_dev_finish, (), amd_stats(amd.scs_amd_aa_dev_get_stats), setting, name), setting, name)

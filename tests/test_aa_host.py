@@ -7,6 +7,7 @@ import pytest
 
 from oracle import pyoracle
 from scs_amd import capi
+from tests import test_aa_dev_gpu as dev  # the loop, the maps and the reference side of the rejected-solve cases
 
 pytestmark = pytest.mark.skipif(not pyoracle.ref_available(), reason="oracle/_ref not built")
 dp = C.POINTER(C.c_double)
@@ -70,3 +71,31 @@ def test_aa_matches_reference_on_a_contraction(type1, reg, relax, mem):
     for (ra, xa), (rr, xr) in zip(ta, tr):
         assert np.abs(xa - xr).max() <= 1e-7 * max(1.0, np.abs(xr).max())
     assert any(v > 0 for v in na)  # some steps were accepted
+
+
+@pytest.mark.parametrize("name", list(dev.REJ_MAPS))
+@pytest.mark.parametrize("setting", list(dev.REJ_SETTINGS))
+def test_rejected_and_degenerate_solves_match_reference(setting, name):
+    """Weight-capped, rank-0 and zero-gamma solves (tests/test_aa_dev_gpu.py, REJ_SETTINGS): counters equal to the
+    reference's aa_get_stats, equal signs of aa_norm, equal safeguard decisions, iterates bit-equal to x <- F(x)."""
+    amd = dev._amd()
+    dev.rej_check(dev.rej_run(amd.scs_amd_aa_init, amd.scs_amd_aa_apply, amd.scs_amd_aa_safeguard, amd.scs_amd_aa_finish, (),
+                              dev.amd_stats(amd.scs_amd_aa_get_stats), setting, name), setting, name)
+
+
+def test_host_core_is_clean_under_the_host_sanitizers(tmp_path):
+    """aa_host.cpp and with it all of aa_small.h, compiled for the HOST alone with AddressSanitizer + UBSan
+    (tests/native/host_sanitize_aa.cpp): rejected, degenerate and accepted solves, no report."""
+    import os
+    import shutil
+    import subprocess
+    if not shutil.which("hipcc"):
+        pytest.skip("hipcc not on PATH")
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "drv")
+    subprocess.check_call(["hipcc", "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-fno-omit-frame-pointer", os.path.join(here, "native", "host_sanitize_aa.cpp"), "-o", exe],
+                          stderr=subprocess.DEVNULL)
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert out.returncode == 0 and "sanitizer driver ok" in out.stdout, out.stdout[-3000:]
+    assert "ERROR: " not in out.stdout and "runtime error" not in out.stdout, out.stdout[-3000:]

@@ -12,6 +12,7 @@ import pytest
 
 from oracle import pyoracle
 from scs_amd import capi
+from tests import test_aa_dev_gpu as dev  # the rejected-solve cases and their reference side
 from tests import test_spmv_exact_gpu as single_suite  # device buffers through the HIP runtime the library links
 
 pytestmark = pytest.mark.gpu
@@ -123,10 +124,10 @@ def _run_single(init, apply, safeguard, reset, finish, extra, cfg, spec, dt=np.f
 class Block:
     """scs_amd_aa_multi_* on host arrays"""
 
-    def __init__(self, L, cfg, K):
+    def __init__(self, L, cfg, K, max_weight=1e10):
         type1, reg, relax, mem, dim = cfg
         self.L, self.T, self.K, self.dim, self.mem = L, L._scs_types, K, dim, mem
-        self.a = L.scs_amd_aa_multi_init(dim, K, mem, mem, type1, reg, relax, 1.0, 1e10, 5)
+        self.a = L.scs_amd_aa_multi_init(dim, K, mem, mem, type1, reg, relax, 1.0, max_weight, 5)
         assert self.a
 
     def _skip(self, skip):
@@ -152,13 +153,13 @@ class Block:
     def reset(self, col):
         self.L.scs_amd_aa_multi_reset(self.a, col)
 
-    def iters(self):
+    def stats(self, k):
         st = self.T.AaStats()
-        out = []
-        for k in range(self.K):
-            self.L.scs_amd_aa_multi_get_stats(self.a, k, C.byref(st))
-            out.append(st.iter)
-        return out
+        self.L.scs_amd_aa_multi_get_stats(self.a, k, C.byref(st))
+        return st
+
+    def iters(self):
+        return [self.stats(k).iter for k in range(self.K)]
 
     def counters(self):
         out = (C.c_longlong * 4)()
@@ -272,6 +273,37 @@ def test_block_matches_single_vector_device_path(cfg_no, K, rejects):
     want = _run_single(L.scs_amd_aa_dev_init, L.scs_amd_aa_dev_apply, L.scs_amd_aa_dev_safeguard, L.scs_amd_aa_dev_reset,
                        L.scs_amd_aa_dev_finish, (), CONFIG[cfg_no], spec)
     _compare(got, want, f"config {cfg_no} K={K} vs aa_dev", rejects)
+
+
+# ---- 2a. rejected and degenerate solves ------------------------------------------------------------------------------------------
+@pytest.mark.skipif(not pyoracle.ref_available(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("setting", list(dev.REJ_SETTINGS))
+def test_a_block_of_rejected_and_degenerate_solves_matches_reference(setting):
+    """The three maps of tests/test_aa_dev_gpu.py (REJ_MAPS) as columns 0, 1, 2 of one block (W = 4): every call holds a
+    weight-capped column beside a rank-0 (setting A) or zero-gamma (setting B) column.  Per column: counters equal to the
+    reference's, equal signs of aa_norm, equal safeguard decisions, iterates bit-equal to x <- F(x)."""
+    type1, reg, mem = dev.REJ_SETTINGS[setting]
+    names = list(dev.REJ_MAPS)
+    K, dim = len(names), dev.REJ_DIM
+    maps = [dev.rej_map(n) for n in names]
+    none = np.zeros(K, bool)
+    with Block(_amd(), (type1, reg, 1.0, mem, dim), K, max_weight=dev.REJ_CAP) as b:
+        assert b.L.scs_amd_aa_multi_width(K) == 4
+        X = np.asfortranarray(np.stack([dev.rej_start(n) for n in names], axis=1))
+        Xp = X.copy(order="F")
+        norms, rejs, traj = [], [], []
+        for i in range(dev.REJ_ITERS):  # the loop of tests/test_aa_dev_gpu.py::_run
+            if i > 0:
+                norms.append(b.apply(X, Xp, none))
+            Xp = X.copy(order="F")
+            for k in range(K):
+                X[:, k] = maps[k](X[:, k])
+            rejs.append(b.safeguard(X, Xp, none))
+            traj.append(X.copy(order="F"))
+        stats = [dev.counters(b.stats(k)) for k in range(K)]
+    for k, name in enumerate(names):
+        dev.rej_check((np.sign([n[k] for n in norms]), [int(r[k]) for r in rejs], [np.ascontiguousarray(t[:, k]) for t in traj],
+                       stats[k]), setting, name)
 
 
 # ---- 3. independence and determinism ---------------------------------------------------------------------------------------------
@@ -431,6 +463,31 @@ def test_bad_arguments_are_refused_with_the_outputs_untouched():
         assert L.scs_amd_aa_multi_safeguard_dev(b.a, None, None, None, rpp) == -1
         assert np.array_equal(_bits(F), _bits(keep)) and (nrm == 7.0).all() and (rej == 7).all()
         assert b.iters() == [0] * 4 and b.counters() == [0] * 4
+
+
+def test_objects_without_memory_do_nothing():
+    """lookback 0: every apply returns 0 and leaves F alone, the safeguard returns 0 -- the single-vector path and blocks alike"""
+    L = _amd()
+    dim = 300
+    rng = np.random.default_rng(4)
+    a = L.scs_amd_aa_dev_init(dim, 0, 0, 1, 1e-8, 1.0, 1.0, 1e10, 5)
+    assert a
+    f, x = rng.standard_normal(dim), rng.standard_normal(dim)
+    keep = f.copy()
+    for _ in range(3):
+        assert L.scs_amd_aa_dev_apply(_p(f), _p(x), a) == 0.0
+        assert L.scs_amd_aa_dev_safeguard(_p(f), _p(x), a) == 0
+    assert np.array_equal(_bits(f), _bits(keep))
+    L.scs_amd_aa_dev_finish(a)
+    for K in (1, 3):
+        with Block(L, (1, 1e-8, 1.0, 0, dim), K) as b:
+            F = np.asfortranarray(rng.standard_normal((dim, K)))
+            X = np.asfortranarray(rng.standard_normal((dim, K)))
+            keep = F.copy(order="F")
+            for _ in range(3):
+                assert (b.apply(F, X, np.zeros(K, bool)) == 0).all()
+                assert (b.safeguard(F, X, np.zeros(K, bool)) == 0).all()
+            assert np.array_equal(_bits(F), _bits(keep)) and b.iters() == [0] * K
 
 
 def test_hip_failure_inside_an_apply():
