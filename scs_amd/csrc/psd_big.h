@@ -3,26 +3,23 @@
 // Replaces LAPACK dsyevr / zheevr + the reconstruction of reference src/cones.c:999-1155 for those blocks; no size
 // limit other than memory.  Included by cones.hip only (uses its RotCS, packed_index, psd_unpack_entry).
 //
-// Per big block (all in HBM, column-major, common leading dimension ld = even-padded largest order):
-//   two copies of A (K2 x K2 working matrix), V (eigenvectors), the carried eigenbasis, a small control record.
-// What ships (rounds 3-4) is the BLOCKED iteration further down: a tournament over 32-wide block columns, one fused launch per outer
-// step (k_bj_fused: the 64 x 64 subproblems of step k + 1 rotated beside the matrix-core update of step k), the cross sweep software-
-// pipelined (bj_inner_sweep_cross).  The single-column form described next is round 2's, kept behind SCS_AMD_PSD_BLOCKED=0 as the
-// baseline of the measurements, and shares the control record, the sweep bookkeeping, the warm start and the reconstruction with it.
-// One Jacobi step = ONE launch over all big blocks (blockIdx.y = block), k_bp_step: A is double-buffered (the step reads
-// the matrix as it stood when the step began and writes the other copy), so every workgroup can form the rotations it
-// needs straight from A without racing the workgroups that are rewriting those entries -- no separate "parameters"
-// launch and no tables.  A workgroup owns a 16 x 16 tile of (row pair, column pair) 2x2 blocks (lanes 0-31 form its 32
-// rotations once, everybody reads them from LDS) or a 64-row x 4-pair tile of V; same formulas, same threshold rule,
-// same round-robin order, same exact zero for a rotated pair's own entry as the LDS kernel.  The running maximum of the
-// off-diagonal entries met in a sweep is an atomic max (order-independent, so still deterministic).
-// k_bp_sweep_end closes a sweep (convergence, sweep cap as in cones.c:1031), the host reads one int per sweep.
-// A step costs ~5 us however small the block (a kernel that hands data to the next one), so the time is steps x sweeps;
-// the earlier two-launch form (parameters, then update) took ~10 us per step.
+// Per big block (all in HBM, column-major, common leading dimension ld = largest order padded to a multiple of 64):
+//   two copies of A (the working matrix), V (eigenvectors), the carried eigenbasis, a small control record.
+// The iteration is a tournament over 32-wide block columns.  A sweep is nbc outer steps, every index pair rotated exactly once: step 0
+// rotates within the block columns, steps 1 .. nbc - 1 pair the block columns round-robin and rotate the cross pairs (bj_pair_sched).
+// One outer step = ONE launch over all big blocks, k_bj_fused: the 64 x 64 subproblems of step k + 1 are rotated in LDS, one workgroup
+// per pair of block columns (bj_inner_sweep_within / bj_inner_sweep_cross, the latter software-pipelined), beside the matrix-core
+// update of step k over the rest of the chip (bj_update_job).  A is double-buffered: a step reads the matrix as it stood when the step
+// began and writes the other copy.  Same formulas, same threshold rule, same exact zero for a rotated pair's own entry as the LDS
+// kernel.  The running maximum of the off-diagonal entries met in a sweep is an atomic max (order-independent, so still
+// deterministic); the last update of a sweep also records the largest off-diagonal entry it leaves, so a sweep that would rotate
+// nothing is never run.  k_bp_sweep_end closes a sweep (convergence, sweep cap as in cones.c:1031); the host enqueues sweeps in
+// batches and reads two ints per batch.  A projection starts from the eigenbasis of the previous one (warm start, k_bp_gemm_tn).
 // Reconstruction X+ = W W' (W = V diag(sqrt(max(lambda, 0)))) runs on the fp64 matrix cores over all CUs (k_bp_gram).
-// Everything is deterministic: no atomics in sums (the one atomic is a max), one workgroup owns every reduction.
+// Everything is deterministic: no atomics in sums (the atomics are maxima), one workgroup owns every reduction.
 //
-// Measured (profiles/r2_bench_psd_sizes_*.jsonl, r3_*, r4_psd_fused_step.md): see DESIGN.md section 6.
+// Measured: DESIGN.md section 3, profiles/r6_psd_big.md and profiles/r4_psd_fused_step.md (which also hold the numbers of the forms
+// this one was chosen over: single-column steps, full 63-step subproblem sweeps, two launches per outer step).
 #pragma once
 
 namespace scsamd {
@@ -31,17 +28,16 @@ struct BigPsdCtl {
   real thr, fro;
   unsigned long long offmax_bits[2]; // bit pattern of the largest |a_pq| met in a sweep (non-negative: orders like the value), by sweep parity:
                                      // the fused step (k_bj_fused) runs the first inner sweep of sweep s + 1 before sweep s is closed
-  unsigned long long left_bits;   // the same of the largest off-diagonal entry of the matrix as the sweep just closed LEFT it (k_bp_offscan)
+  unsigned long long left_bits;   // the same of the largest off-diagonal entry of the matrix as the sweep just closed LEFT it (bj_update_job)
   int cur[2];                     // which A copy holds the block before launch g: cur[g & 1] (written for g+1 by the launch itself)
   int done, sweeps, kraw; // kraw: signed order (negative = complex embedding), copied here so that a step kernel
                           // needs ONE dependent read (this record) before it touches A
 };
 
 constexpr int BP_THREADS = 256;
-constexpr int BP_PARAM_THREADS = 1024;
 
 struct BigPsdView {
-  int nbig, ld;           // blocks, common leading dimension (= K2 of the largest)
+  int nbig, ld;           // blocks, common leading dimension (= K64 of the largest)
   const int *id;          // index of each big block in psd_off / psd_k
   const int *psd_off, *psd_k;
   real *A, *V;            // nbig * ld * ld each (A: copy 0 of the working matrix)
@@ -49,12 +45,12 @@ struct BigPsdView {
   BigPsdCtl *ctl;         // nbig
 };
 
-constexpr int BJ_B = 32;       // blocked iteration: width of a block column
+constexpr int BJ_B = 32;       // width of a block column
 constexpr int BJ_W = 2 * BJ_B; // order of the subproblem of a pair of block columns
 
 struct BlockShape {
-  int k, K2, nn, npairs;
-  int K64, nbc; // blocked iteration: order padded to whole pairs of block columns, number of block columns (even)
+  int k, K2, nn;
+  int K64, nbc; // order padded to whole pairs of block columns, number of block columns (even)
   bool cplx;
 };
 __device__ __forceinline__ BlockShape bp_shape_raw(int kraw) {
@@ -63,7 +59,6 @@ __device__ __forceinline__ BlockShape bp_shape_raw(int kraw) {
   s.k = s.cplx ? -kraw : kraw;
   s.nn = s.k / 2;
   s.K2 = (s.k + 1) & ~1;
-  s.npairs = s.K2 / 2;
   s.K64 = (s.k + BJ_W - 1) / BJ_W * BJ_W;
   s.nbc = s.K64 / BJ_B;
   return s;
@@ -71,12 +66,12 @@ __device__ __forceinline__ BlockShape bp_shape_raw(int kraw) {
 __device__ __forceinline__ BlockShape bp_shape(const BigPsdView &B, int b) { return bp_shape_raw(B.psd_k[B.id[b]]); }
 
 // A <- unpacked block (diagonal * sqrt 2), V <- I
-__global__ __launch_bounds__(BP_THREADS) void k_bp_unpack(BigPsdView B, const real *__restrict__ x, int set_identity, int blocked) {
+__global__ __launch_bounds__(BP_THREADS) void k_bp_unpack(BigPsdView B, const real *__restrict__ x, int set_identity) {
   const int b = blockIdx.y;
   const BlockShape s = bp_shape(B, b);
   const real *X = x + B.psd_off[B.id[b]];
   real *A = B.A + (size_t)b * B.ld * B.ld, *V = B.V + (size_t)b * B.ld * B.ld;
-  const int span = blocked ? s.K64 : s.K2; // the blocked iteration works on whole pairs of block columns: zero rows / columns, unit diagonal in V
+  const int span = s.K64; // the iteration works on whole pairs of block columns: zero rows / columns, unit diagonal in V
   const long long total = (long long)span * span;
   for (long long e = (long long)blockIdx.x * BP_THREADS + threadIdx.x; e < total; e += (long long)gridDim.x * BP_THREADS) {
     const int i = (int)(e % span), j = (int)(e / span);
@@ -133,158 +128,35 @@ __device__ __forceinline__ real bp_from_bits(unsigned long long b) {
   return sizeof(real) == 8 ? (real)__longlong_as_double((long long)b) : (real)__uint_as_float((unsigned)b);
 }
 
-// rotation of pair i of round-robin step `step`, from the matrix as it stands before the step
-__device__ __forceinline__ void bp_rotation(const real *Aold, size_t ld, int i, int step, int K2, int k, real thr, int2 &pq,
-                                            RotCS &cs, real &aa_out) {
-  int p = i == 0 ? 0 : 1 + ((i - 1 + step) % (K2 - 1));
-  int q = 1 + ((K2 - 2 - i + step) % (K2 - 1));
-  if (p > q) {
-    const int t = p;
-    p = q;
-    q = t;
-  }
-  real c = 1, s = 0;
-  const real apq = Aold[q * ld + p], aqq = Aold[q * ld + q], app = Aold[p * ld + p];
-  const real aa = absval(apq);
-  aa_out = q < k ? aa : (real)0;
-  if (q < k && aa > thr) {
-    // t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (aqq - app) / (2 apq), written without the first division
-    const real d = aqq - app, bb = (real)2 * apq;
-    jacobi_cs(d, bb, c, s);
-  }
-  pq = make_int2(p, q);
-  cs = RotCS{c, s};
-}
-
-constexpr int BP_TILE = 16;   // a workgroup's tile of 2x2 blocks: 16 row pairs x 16 column pairs
-constexpr int BP_VROWS = 64;  // V tile: 64 rows x 4 pairs
-constexpr int BP_VPAIRS = BP_THREADS / BP_VROWS;
-
-// arg = (launch parity) | (round-robin step << 1): the control record's `cur` is double-buffered by LAUNCH parity (a sweep
-// of the largest block has an odd or even number of steps), the pairing follows the step
-__global__ __launch_bounds__(BP_THREADS) void k_bp_step(BigPsdView B, int arg) {
-  const int slot = arg & 1, step = arg >> 1;
-  __shared__ int2 s_pq[2 * BP_TILE];
-  __shared__ RotCS s_cs[2 * BP_TILE];
-  const int b = blockIdx.y, tid = threadIdx.x;
-  BigPsdCtl *ctl = B.ctl + b;
-  const int done = ctl->done, kraw = ctl->kraw, cur = ctl->cur[slot];
-  const real thr = ctl->thr;
-  const BlockShape sh = bp_shape_raw(kraw);
-  const bool active = !done && step < sh.K2 - 1; // a block smaller than the largest has fewer steps per sweep
-  if (blockIdx.x == 0 && tid == 0) ctl->cur[slot ^ 1] = active ? cur ^ 1 : cur;
-  if (!active) return;
-  const size_t ld = B.ld, mat = (size_t)b * ld * ld;
-  const real *Aold = (cur ? B.A1 : B.A) + mat;
-  real *Anew = (cur ? B.A : B.A1) + mat;
-  real *V = B.V + mat;
-  const int npairs = sh.npairs, K2 = sh.K2, k = sh.k;
-  const int TP = (npairs + BP_TILE - 1) / BP_TILE;
-  const int nta = TP * TP;
-  const int TQv = (npairs + BP_VPAIRS - 1) / BP_VPAIRS, TR = (K2 + BP_VROWS - 1) / BP_VROWS;
-  int tile = blockIdx.x;
-  if (tile < nta) {
-    // ---- A <- J' A J on a 16 x 16 tile of 2x2 blocks: rows of pairs [16 tp, +16), columns of pairs [16 tq, +16)
-    const int tq = tile / TP, tp = tile % TP;
-    if (tid < 2 * BP_TILE) {
-      const int i = tid < BP_TILE ? BP_TILE * tp + tid : BP_TILE * tq + (tid - BP_TILE);
-      int2 pq = make_int2(0, 0);
-      RotCS cs{(real)1, (real)0};
-      real aa = 0;
-      if (i < npairs) bp_rotation(Aold, ld, i, step, K2, k, thr, pq, cs, aa);
-      s_pq[tid] = pq;
-      s_cs[tid] = cs;
-      // every pair is a "row pair" of exactly the tiles with tq == 0: they carry the sweep's off-diagonal maximum
-      if (tq == 0 && tid < BP_TILE) {
-        real mx = aa;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-          const real w = __shfl_down(mx, o, 64);
-          mx = w > mx ? w : mx;
-        }
-        if (tid == 0 && mx > (real)0) atomicMax(&ctl->offmax_bits[ctl->sweeps & 1], bp_bits(mx));
-      }
-    }
-    __syncthreads();
-    const int lp = tid & (BP_TILE - 1), lq = tid >> 4;
-    const int P = BP_TILE * tp + lp, Q = BP_TILE * tq + lq;
-    if (P < npairs && Q < npairs) {
-      // consecutive lanes walk the ROW pairs: consecutive p1 (and q1) -> consecutive addresses in column-major storage
-      const int2 pq1 = s_pq[lp], pq2 = s_pq[BP_TILE + lq];
-      const RotCS r1 = s_cs[lp], r2 = s_cs[BP_TILE + lq];
-      const int p1 = pq1.x, q1 = pq1.y, p2 = pq2.x, q2 = pq2.y;
-      const real c1 = r1.c, s1 = r1.s, c2 = r2.c, s2 = r2.s;
-      const size_t i11 = p2 * ld + p1, i12 = q2 * ld + p1, i21 = p2 * ld + q1, i22 = q2 * ld + q1;
-      const real a11 = Aold[i11], a12 = Aold[i12], a21 = Aold[i21], a22 = Aold[i22];
-      const real r11 = c1 * a11 - s1 * a21, r12 = c1 * a12 - s1 * a22;
-      const real r21 = s1 * a11 + c1 * a21, r22 = s1 * a12 + c1 * a22;
-      const bool own = P == Q && s1 != (real)0; // the rotated pair's own off-diagonal entry: exact zero
-      Anew[i11] = c2 * r11 - s2 * r12;
-      Anew[i12] = own ? (real)0 : s2 * r11 + c2 * r12;
-      Anew[i21] = own ? (real)0 : c2 * r21 - s2 * r22;
-      Anew[i22] = s2 * r21 + c2 * r22;
-    }
-    return;
-  }
-  tile -= nta;
-  if (tile >= TQv * TR) return;
-  // ---- V <- V J on a tile of 64 rows x 4 pairs (in place: a lane owns its two entries)
-  const int tqv = tile / TR, tr = tile % TR;
-  if (tid < BP_VPAIRS) {
-    const int i = BP_VPAIRS * tqv + tid;
-    int2 pq = make_int2(0, 0);
-    RotCS cs{(real)1, (real)0};
-    real aa = 0;
-    if (i < npairs) bp_rotation(Aold, ld, i, step, K2, k, thr, pq, cs, aa);
-    s_pq[tid] = pq;
-    s_cs[tid] = cs;
-  }
-  __syncthreads();
-  const int li = tid & (BP_VROWS - 1), lq = tid >> 6;
-  const int row = BP_VROWS * tr + li, Q = BP_VPAIRS * tqv + lq;
-  if (row < K2 && Q < npairs) {
-    const int2 pq2 = s_pq[lq];
-    const RotCS r2 = s_cs[lq];
-    if (r2.s != (real)0) {
-      const size_t ip = pq2.x * ld + row, iq = pq2.y * ld + row;
-      const real vp = V[ip], vq = V[iq];
-      V[ip] = r2.c * vp - r2.s * vq;
-      V[iq] = r2.s * vp + r2.c * vq;
-    }
-  }
-}
-
 // =====================================================================================================================
-// Blocked iteration: the round-robin tournament runs over BLOCK COLUMNS of width 32 instead of single
-// columns.  One outer step pairs the block columns (I, J); for every pair
-//   k_bj_inner   one workgroup pulls the 64 x 64 subproblem S = A[IJ, IJ] into LDS, runs ONE sweep of the same parallel
-//                cyclic Jacobi rotations as k_psd_jacobi on it (63 inner steps, same formulas, same threshold, exact zero
-//                for a rotated pair's own entry) and leaves the accumulated orthogonal factor Q (64 x 64), the rotated
-//                subproblem S' = Q' S Q and a "rotated at all" flag in HBM;
-//   k_bj_update  applies the step to the whole matrix on the fp64 matrix cores: tile (P, Q) of the double-buffered A
+// The tournament runs over BLOCK COLUMNS of width 32, not single columns.  One outer step pairs the block columns
+// (I, J); for every pair
+//   the inner sweep  one workgroup pulls the 64 x 64 subproblem S = A[IJ, IJ] into LDS, runs the same parallel cyclic Jacobi rotations
+//                as k_psd_jacobi on it (31 or 32 inner steps, same formulas, same threshold, exact zero for a rotated pair's own
+//                entry) and leaves the accumulated orthogonal factor Q (64 x 64), the rotated subproblem S' = Q' S Q and a
+//                "rotated at all" flag in HBM;
+//   the update   applies the step to the whole matrix on the fp64 matrix cores: tile (P, Q) of the double-buffered A
 //                becomes Q_P' A[P, Q] Q_Q (two 64^3 products per workgroup, operands staged in LDS with a leading
 //                dimension of 66 so that the v_mfma_f64_16x16x4 operand reads are bank-conflict free), the diagonal tiles
 //                take S' as the inner sweep left it (rotation arithmetic keeps its tiny entries relatively accurate and
 //                its zeros exact; a GEMM would refill them with rounding noise of the diagonal's size), and the
 //                eigenvector tiles V[:, Q] <- V[:, Q] Q_Q.
-// A sweep is nbc - 1 outer steps of two launches each instead of K - 1 launches (1024 x 1024: 62 launches instead of 1023)
-// and the O(K^3) work of a sweep moves onto the matrix cores.  Convergence (largest off-diagonal entry met during a sweep
-// <= eps |A|_F / k), sweep cap, warm start and reconstruction are unchanged.  Padding rows / columns (order rounded up to a
-// multiple of 64) are zero in A and unit in V; a rotation never touches them (q < k, as in the LDS kernel).
+// A sweep is nbc launches instead of one per column (1024 x 1024: 32 instead of 1023) and its O(K^3) work runs on the matrix
+// cores.  Convergence (largest off-diagonal entry met during a sweep <= eps |A|_F / k), sweep cap, warm start and reconstruction
+// are those of the LDS kernel.  Padding rows / columns (order rounded up to a multiple of 64) are zero in A and unit in V; a
+// rotation never touches them (q < k, as in the LDS kernel).
 constexpr int BJ_LD = BJ_W + 2;        // LDS leading dimension of the product operands (66: rows 2 banks apart)
 constexpr int BJ_ILD = BJ_W | 1;       // LDS leading dimension of the rotation sweep (65: row and column walks conflict free)
-#ifndef BJ_INNER_THREADS_OVERRIDE
-constexpr int BJ_INNER_THREADS = 512;
-#else
-constexpr int BJ_INNER_THREADS = BJ_INNER_THREADS_OVERRIDE;
-#endif
-constexpr int BJ_UPD_THREADS_MAX = 1024;                // largest workgroup that runs bj_inner_sweep (k_bj_fused)
+constexpr int BJ_INNER_THREADS = 512;                   // lanes of the workgroup that carry an inner sweep's updates
+// k_bj_fused's workgroup, sixteen waves.  Update: one 16 x 16 output tile each per product (measured 1024 x 1024: 26.1 / 24.6 / 23.8 ms
+// at 256 / 512 / 1024).  Cross sweep: eight waves update, one forms the next step's rotations, the rest keep the barriers company.
+constexpr int BJ_UPD_THREADS = 1024;
 constexpr int BJ_NBLK = BJ_B * BJ_B / BJ_INNER_THREADS; // 2x2 blocks of S per lane and inner step
 constexpr int BJ_NROW = BJ_W * BJ_B / BJ_INNER_THREADS; // row pairs of Q per lane and inner step
-static_assert(BJ_NBLK * BJ_INNER_THREADS == BJ_B * BJ_B && BJ_NROW * BJ_INNER_THREADS == BJ_W * BJ_B, "k_bj_inner: whole items per lane");
+static_assert(BJ_NBLK * BJ_INNER_THREADS == BJ_B * BJ_B && BJ_NROW * BJ_INNER_THREADS == BJ_W * BJ_B, "bj_inner_sweep_within: whole items per lane");
 constexpr size_t BJ_INNER_LDS = (size_t)3 * BJ_W * BJ_ILD * sizeof(real) + 2 * BJ_B * sizeof(RotCS); // S (two copies), Q, two generations of (c, s)
-constexpr int BJ_INNER_LAUNCH = 1024; // (= BJ_UPD_THREADS_MAX) the cross sweep's workgroup: fifteen worker waves and the wave that forms the rotations
-constexpr size_t BJ_UPDATE_LDS = (size_t)4 * BJ_W * BJ_LD * sizeof(real);
+constexpr size_t BJ_UPDATE_LDS = (size_t)4 * BJ_W * BJ_LD * sizeof(real);                            // k_bj_fused's dynamic LDS: the update's four operands
+static_assert(BJ_INNER_LDS <= BJ_UPDATE_LDS, "k_bj_fused: the inner sweeps work in the update's LDS");
 
 __device__ __forceinline__ int2 bj_pair(int i, int step, int nbc) { // round robin over block columns, as over columns
   int I = i == 0 ? 0 : 1 + ((i - 1 + step) % (nbc - 1));
@@ -296,43 +168,21 @@ __device__ __forceinline__ int2 bj_pair(int i, int step, int nbc) { // round rob
   }
   return make_int2(I, J);
 }
-// The sweep's schedule (SCS_AMD_PSD_CROSS, default on): outer step 0 pairs the block columns (0,1), (2,3), ... and rotates only WITHIN
-// each block column (two independent round robins over 32 indices, 31 inner steps); outer steps 1 .. nbc - 1 are the tournament over
-// block columns and rotate only the CROSS pairs (p in I, q in J; 32 inner steps of the cyclic shift q = (i + st) mod 32): every index
-// pair is rotated exactly once per sweep -- a cyclic Jacobi ordering -- instead of the within-block pairs once per outer step.
-// The numpy emulation of this schedule needs 10 - 12 sweeps where the full 63-step subproblem sweep needs 8 - 10; an outer step costs
-// half.  ostep = the `step` field of a launch: 0 = the within pass, s >= 1 = tournament step s - 1 (cross schedule); with the full
-// schedule ostep = tournament step, no within pass.
-__device__ __forceinline__ int2 bj_pair_sched(int i, int ostep, int nbc, int cross) {
-  if (!cross) return bj_pair(i, ostep, nbc);
+// The sweep's schedule: outer step 0 pairs the block columns (0,1), (2,3), ... and rotates only WITHIN each block column (two
+// independent round robins over 32 indices, 31 inner steps); outer steps 1 .. nbc - 1 are the tournament over block columns and
+// rotate only the CROSS pairs (p in I, q in J; 32 inner steps of the cyclic shift q = (i + st) mod 32): every index pair is rotated
+// exactly once per sweep -- a cyclic Jacobi ordering.  (Full 63-step sweeps of every subproblem rotated the within-block pairs once
+// per outer step: 8 - 10 sweeps instead of 10 - 12 in the numpy emulation, but an outer step cost twice as much.)
+// ostep = the `step` field of a launch: 0 = the within pass, s >= 1 = tournament step s - 1.
+__device__ __forceinline__ int2 bj_pair_sched(int i, int ostep, int nbc) {
   if (ostep == 0) return make_int2(2 * i, 2 * i + 1);
   return bj_pair(i, ostep - 1, nbc);
 }
-__device__ __forceinline__ int bj_outer_steps(int nbc, int cross) { return cross ? nbc : nbc - 1; }
-// pair i (0..31) of inner step st for the three kinds of inner sweep
-__device__ __forceinline__ int2 bj_inner_pair(int i, int st, int kind) { // kind 0: full round robin over 64; 1: within; 2: cross
-  int p, q;
-  if (kind == 2) {
-    p = i;
-    q = BJ_B + ((i + st) & (BJ_B - 1));
-  } else {
-    const int n = kind == 1 ? BJ_B : BJ_W, j = kind == 1 ? (i & (BJ_B / 2 - 1)) : i, off = kind == 1 && i >= BJ_B / 2 ? BJ_B : 0;
-    p = j == 0 ? 0 : 1 + ((j - 1 + st) % (n - 1));
-    q = 1 + ((n - 2 - j + st) % (n - 1));
-    if (p > q) {
-      const int t = p;
-      p = q;
-      q = t;
-    }
-    p += off;
-    q += off;
-  }
-  return make_int2(p, q);
-}
-template <int KIND> __device__ __forceinline__ int2 bj_inner_pair_k(int i, int st) { // the same with the kind known at compile time (no run-time modulus)
-  if (KIND == 2) return make_int2(i, BJ_B + ((i + st) & (BJ_B - 1)));
-  constexpr int n = KIND == 1 ? BJ_B : BJ_W;
-  const int j = KIND == 1 ? (i & (BJ_B / 2 - 1)) : i, off = KIND == 1 && i >= BJ_B / 2 ? BJ_B : 0;
+// pair i (0..31) of inner step st of the within sweep: pairs 0 .. 15 are a round robin over the local indices 0 .. 31, pairs 16 .. 31
+// the same over 32 .. 63.  (The cross sweep's pair i is (i, 32 + (i + st) mod 32).)
+__device__ __forceinline__ int2 bj_within_pair(int i, int st) {
+  constexpr int n = BJ_B;
+  const int j = i & (BJ_B / 2 - 1), off = i >= BJ_B / 2 ? BJ_B : 0;
   int p = j == 0 ? 0 : 1 + ((j - 1 + st) % (n - 1));
   int q = 1 + ((n - 2 - j + st) % (n - 1));
   if (p > q) {
@@ -345,27 +195,26 @@ template <int KIND> __device__ __forceinline__ int2 bj_inner_pair_k(int i, int s
 // global row / column of local index l (0..63) of the pair (I, J)
 __device__ __forceinline__ int bj_gidx(int2 IJ, int l) { return l < BJ_B ? IJ.x * BJ_B + l : IJ.y * BJ_B + (l - BJ_B); }
 
-// The inner sweep proper, on the subproblem already in LDS (S[r * BJ_ILD + c]); Q <- I here.  Every thread of the workgroup calls it;
+// The WITHIN sweep (outer step 0), on the subproblem already in LDS (S[r * BJ_ILD + c]); Q <- I here.  Every thread of the workgroup calls it;
 // threads beyond BJ_INNER_THREADS only keep the barriers company (the fused step runs it in a workgroup of BJ_UPD_THREADS).
 // Leaves Q, S' and the "rotated at all" flag in HBM (Qg / Sg: 64 x 64 column-major) and the sweep's off-diagonal maximum in the
 // control record (slot `offslot`).
 // A step is two phases and two barriers: 32 lanes form the rotations (three LDS reads, fp64 rsqrt chain: ~840 clocks measured), then
 // 1024 2x2 blocks of S and 2048 row pairs of Q over the lanes: every lane owns BJ_NBLK blocks and BJ_NROW row pairs and asks for
 // everything it needs -- the (c, s) of its pairs, its operands, the "any rotation" flag -- in ONE batch of LDS reads: the pair indices
-// are arithmetic (the kind of sweep is a template parameter), so no address depends on a table.  (With the pairs read from a table
+// are arithmetic (bj_within_pair), so no address depends on a table.  (With the pairs read from a table
 // the phase was three dependent LDS round trips: 1830 clocks.)
-template <int KIND>
-__device__ __forceinline__ void bj_inner_sweep_k(unsigned char *smem, int2 IJ, int k, real thr, BigPsdCtl *ctl, int offslot, real *Qg, real *Sg,
-                                                 int *flag_out) {
+__device__ __forceinline__ void bj_inner_sweep_within(unsigned char *smem, int2 IJ, int k, real thr, BigPsdCtl *ctl, int offslot, real *Qg, real *Sg,
+                                                      int *flag_out) {
   real *S = reinterpret_cast<real *>(smem);
   real *Q = S + 2 * BJ_W * BJ_ILD; // (the second copy of S between them is the cross sweep's)
   RotCS *rot_cs = reinterpret_cast<RotCS *>(Q + BJ_W * BJ_ILD);
-  __shared__ real red[BJ_UPD_THREADS_MAX / SCSAMD_WAVE];
+  __shared__ real red[BJ_UPD_THREADS / SCSAMD_WAVE];
   __shared__ int rot_any[2]; // (plain LDS accesses; a volatile flag is reached through FLAT loads / stores with system scope)
   __shared__ int rotated;
   const int tid = threadIdx.x, nthr = blockDim.x;
   const bool worker = tid < BJ_INNER_THREADS;
-  constexpr int nst = KIND == 0 ? BJ_W - 1 : (KIND == 1 ? BJ_B - 1 : BJ_B);
+  constexpr int nst = BJ_B - 1;
   for (int e = tid; e < BJ_W * BJ_W; e += nthr) {
     const int r = e & (BJ_W - 1), c = e >> 6;
     Q[r * BJ_ILD + c] = r == c ? (real)1 : (real)0;
@@ -378,7 +227,7 @@ __device__ __forceinline__ void bj_inner_sweep_k(unsigned char *smem, int2 IJ, i
     const int par = st & 1;
     if (tid < NP) {
       const int i = tid;
-      const int2 pq_i = bj_inner_pair_k<KIND>(i, st);
+      const int2 pq_i = bj_within_pair(i, st);
       const int p = pq_i.x, q = pq_i.y;
       real c = 1, s = 0;
       const real apq = S[p * BJ_ILD + q], aqq = S[q * BJ_ILD + q], app = S[p * BJ_ILD + p];
@@ -401,7 +250,7 @@ __device__ __forceinline__ void bj_inner_sweep_k(unsigned char *smem, int2 IJ, i
 #pragma unroll
       for (int u = 0; u < BJ_NBLK; ++u) {
         const int e = tid + u * BJ_INNER_THREADS, Qi = e / NP, P = e % NP;
-        const int2 pq1 = bj_inner_pair_k<KIND>(P, st), pq2 = bj_inner_pair_k<KIND>(Qi, st);
+        const int2 pq1 = bj_within_pair(P, st), pq2 = bj_within_pair(Qi, st);
         i11[u] = pq1.x * BJ_ILD + pq2.x;
         i12[u] = pq1.x * BJ_ILD + pq2.y;
         i21[u] = pq1.y * BJ_ILD + pq2.x;
@@ -417,7 +266,7 @@ __device__ __forceinline__ void bj_inner_sweep_k(unsigned char *smem, int2 IJ, i
 #pragma unroll
       for (int j = 0; j < BJ_NROW; ++j) {
         const int f = tid + j * BJ_INNER_THREADS, Qi = f / BJ_W, i = f % BJ_W;
-        const int2 pq2 = bj_inner_pair_k<KIND>(Qi, st);
+        const int2 pq2 = bj_within_pair(Qi, st);
         ip[j] = i * BJ_ILD + pq2.x;
         iq[j] = i * BJ_ILD + pq2.y;
         rq[j] = rot_cs[Qi];
@@ -459,16 +308,6 @@ __device__ __forceinline__ void bj_inner_sweep_k(unsigned char *smem, int2 IJ, i
     Sg[c * BJ_W + r] = S[r * BJ_ILD + c];
   }
 }
-// (measurement knobs of the cross sweep; the defaults are what ships)
-#ifndef BJ_AHEAD_PRIO
-#define BJ_AHEAD_PRIO 3
-#endif
-#ifndef BJ_AHEAD_ONE_BATCH
-#define BJ_AHEAD_ONE_BATCH 1
-#endif
-#ifndef BJ_AHEAD_ANY_LATE
-#define BJ_AHEAD_ANY_LATE 1
-#endif
 // one 2x2 block of J' S J: rows rotated by (c1, s1), then columns by (c2, s2); `own`: the block of a rotated pair with itself, whose
 // off-diagonal entries are exact zeros.  ONE definition (explicit fused multiply-adds) for the lanes that update S and the lanes that
 // look one step ahead, so that both get the same bits.
@@ -487,7 +326,7 @@ __device__ __forceinline__ Blk2 bj_block(real a11, real a12, real a21, real a22,
 }
 
 // The CROSS sweep (pairs p in I, q in J; 32 steps; 31 of the 32 launches of a sweep of a 1024 x 1024 block).  Three things set it apart
-// from the generic sweep above (measurements: profiles/r4_psd_fused_step.md):
+// from the within sweep above (measurements: profiles/r4_psd_fused_step.md):
 //  * software pipeline: the rotations of step st + 1 are formed DURING the update of step st by a wave that does nothing else (the
 //    two-phase step is 910 clocks of rotations -- an LDS round trip, the rsqrt chain, a barrier -- plus 2020 of update).  S is double-
 //    buffered (the update reads one copy and writes the other), so the look-ahead lanes can read the old entries while they are being
@@ -507,12 +346,12 @@ __device__ __forceinline__ void bj_inner_sweep_cross(unsigned char *smem, int2 I
   real *S0 = reinterpret_cast<real *>(smem);
   real *Q = S0 + 2 * BJ_W * BJ_ILD;                              // only its J columns (32 .. 63) are used here
   RotCS *rot_cs = reinterpret_cast<RotCS *>(Q + BJ_W * BJ_ILD); // [2][BJ_B]: generation st & 1 holds the rotations of step st
-  __shared__ real red[BJ_UPD_THREADS_MAX / SCSAMD_WAVE];
+  __shared__ real red[BJ_UPD_THREADS / SCSAMD_WAVE];
   __shared__ int rot_any[2]; // generation st & 1: does step st rotate anything?
   __shared__ int rotated;
-  const int tid = threadIdx.x, nthr = blockDim.x; // nthr == BJ_UPD_THREADS_MAX
+  const int tid = threadIdx.x, nthr = blockDim.x; // nthr == BJ_UPD_THREADS
   constexpr int nst = BJ_B;
-  constexpr int AHEAD0 = BJ_UPD_THREADS_MAX - SCSAMD_WAVE, NOFF = BJ_B * (BJ_B - 1) / 2;
+  constexpr int AHEAD0 = BJ_UPD_THREADS - SCSAMD_WAVE, NOFF = BJ_B * (BJ_B - 1) / 2;
   const bool ahead = tid >= AHEAD0;       // the wave that forms the rotations (its two halves do the same work: no divergence; the lanes vote)
   const int ai = (tid - AHEAD0) & (BJ_B - 1), aj = (ai + 1) & (BJ_B - 1);
   // ---- this lane's items, fixed for the sweep.  Waves 0-7: one block of S (lanes 0 .. 495 the off-diagonal blocks P < Q, lanes 496 .. 511
@@ -574,7 +413,7 @@ __device__ __forceinline__ void bj_inner_sweep_cross(unsigned char *smem, int2 I
     ahead_offsets(0);
   }
   __syncthreads();
-  if (BJ_AHEAD_PRIO && ahead) __builtin_amdgcn_s_setprio(BJ_AHEAD_PRIO);
+  if (ahead) __builtin_amdgcn_s_setprio(3);
   int cur = 0;
   for (int st = 0; st < nst; ++st) {
     const int gen = st & 1;
@@ -626,21 +465,14 @@ __device__ __forceinline__ void bj_inner_sweep_cross(unsigned char *smem, int2 I
       const real e11 = Sr[ao[3]], e12 = Sr[ao[4]], e22 = Sr[ao[5]];
       const real f11 = Sr[ao[6]], f12 = Sr[ao[7]], f21 = Sr[ao[8]], f22 = Sr[ao[9]];
       const RotCS ri = cs[ai], rj = cs[aj];
-#if BJ_AHEAD_ANY_LATE
       any = rot_any[gen];
-#endif
-#if BJ_AHEAD_ONE_BATCH
       __builtin_amdgcn_sched_barrier(0); // all reads in ONE round trip (left to itself the scheduler split them into three)
-#endif
       const int qn = BJ_B + ((ai + st + 1) & (BJ_B - 1));
       const Blk2 bd = bj_block(d11, d12, d12, d22, ri, ri, ri.s != (real)0);
       const Blk2 be = bj_block(e11, e12, e12, e22, rj, rj, rj.s != (real)0);
       const Blk2 bf = bj_block(f11, f12, f21, f22, ai < aj ? ri : rj, ai < aj ? rj : ri, false);
       BJ_FORM(gen ^ 1, qn, bd.n11, be.n22, ai < aj ? bf.n12 : bf.n21);
       ahead_offsets(st + 1);
-#if !BJ_AHEAD_ANY_LATE
-      any = rot_any[gen];
-#endif
     } else {
       any = rot_any[gen];
     }
@@ -669,41 +501,6 @@ __device__ __forceinline__ void bj_inner_sweep_cross(unsigned char *smem, int2 I
   }
 }
 
-__device__ __forceinline__ void bj_inner_sweep(unsigned char *smem, int2 IJ, int kind, int k, real thr, BigPsdCtl *ctl, int offslot, real *Qg,
-                                               real *Sg, int *flag_out) {
-  if (kind == 2) bj_inner_sweep_cross(smem, IJ, k, thr, ctl, offslot, Qg, Sg, flag_out);
-  else if (kind == 1) bj_inner_sweep_k<1>(smem, IJ, k, thr, ctl, offslot, Qg, Sg, flag_out);
-  else bj_inner_sweep_k<0>(smem, IJ, k, thr, ctl, offslot, Qg, Sg, flag_out);
-}
-
-// Qbuf / Sbuf: per (block, pair) 64 x 64 column-major; Qflag: 1 if the sweep rotated anything
-__global__ __launch_bounds__(BJ_INNER_LAUNCH) void k_bj_inner(BigPsdView B, real *Qbuf, real *Sbuf, int *Qflag, int npmax, int arg, int cross) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char bj_smem[];
-  real *S = reinterpret_cast<real *>(bj_smem);
-  const int slot = arg & 1, step = arg >> 1;
-  const int b = blockIdx.y, pi = blockIdx.x, tid = threadIdx.x;
-  BigPsdCtl *ctl = B.ctl + b;
-  const int done = ctl->done, kraw = ctl->kraw, cur = ctl->cur[slot];
-  const real thr = ctl->thr;
-  const BlockShape sh = bp_shape_raw(kraw);
-  if (done || step >= bj_outer_steps(sh.nbc, cross) || pi >= sh.nbc / 2) return;
-  const int2 IJ = bj_pair_sched(pi, step, sh.nbc, cross);
-  const int kind = !cross ? 0 : (step == 0 ? 1 : 2);
-  const size_t ld = B.ld, mat = (size_t)b * ld * ld;
-  const real *Aold = (cur ? B.A1 : B.A) + mat;
-  for (int e = tid; e < BJ_W * BJ_W; e += BJ_INNER_LAUNCH) {
-    const int r = e & (BJ_W - 1), c = e >> 6; // r fast: 32-entry runs of a column of A
-    S[r * BJ_ILD + c] = Aold[(size_t)bj_gidx(IJ, c) * ld + bj_gidx(IJ, r)];
-  }
-  const size_t slot_q = ((size_t)b * npmax + pi);
-  bj_inner_sweep(bj_smem, IJ, kind, sh.k, thr, ctl, ctl->sweeps & 1, Qbuf + slot_q * BJ_W * BJ_W, Sbuf + slot_q * BJ_W * BJ_W, Qflag + slot_q);
-}
-
-#ifndef BJ_UPD_THREADS_OVERRIDE
-constexpr int BJ_UPD_THREADS = 1024; // sixteen waves: one 16 x 16 output tile each per product (measured 1024 x 1024: 26.1 / 24.6 / 23.8 ms at 256 / 512 / 1024)
-#else
-constexpr int BJ_UPD_THREADS = BJ_UPD_THREADS_OVERRIDE;
-#endif
 // O[i][j] = sum_k L[i][k] R[k][j] for operands in LDS, 64 summation indices, i < 16 mt, j < 16 nt: L[i][k] at L[i * BJ_LD + k], R[k][j] at
 // R[j * BJ_LD + k] (both contiguous along the summation index), O[i][j] at O[j * BJ_LD + i].  16 x 16 output tiles dealt to the waves;
 // lane (li = l & 15, lk = l >> 4) supplies L[16 ti + li][4 ks + lk] and R[4 ks + lk][16 tj + li].  An output entry is the same sequence of
@@ -734,19 +531,19 @@ __device__ __forceinline__ void bj_gemm64(const real *L, const real *R, real *O,
 
 // one tile of the step `step` of block b: tile < nta -> A tile (P <= Q) and its mirror, else a V tile.  smem: 4 x 64 x BJ_LD reals.
 // left_bits (round 6; the LAST step of the block's sweep only, else null): the largest off-diagonal entry this job writes goes there --
-// the sweep's closing reads off it whether another sweep would rotate anything (see k_bp_offscan, which does the same as a pass of its
-// own for the forms that do not come through here), at the price of one atomic per workgroup instead of a launch per sweep.
+// the sweep's closing (k_bp_sweep_end) reads off it whether another sweep would rotate anything, at the price of one atomic per
+// workgroup instead of a pass over the matrix per sweep.
 __device__ __forceinline__ void bj_update_job(const BigPsdView &B, unsigned char *smem, const real *__restrict__ Qbuf, const real *__restrict__ Sbuf,
-                                              const int *__restrict__ Qflag, int npmax, int b, int tile, int step, int cross, const BlockShape &sh,
+                                              const int *__restrict__ Qflag, int npmax, int b, int tile, int step, const BlockShape &sh,
                                               const real *Aold, real *Anew, real *V, unsigned long long *left_bits = nullptr) {
   real *xs = reinterpret_cast<real *>(smem);
   real *qp = xs + BJ_W * BJ_LD, *qq = qp + BJ_W * BJ_LD, *ts = qq + BJ_W * BJ_LD;
-  __shared__ real red_left[BJ_UPD_THREADS_MAX / SCSAMD_WAVE];
+  __shared__ real red_left[BJ_UPD_THREADS / SCSAMD_WAVE];
   const int tid = threadIdx.x;
   const size_t ld = B.ld;
   // Only the tiles (P, Q) with P <= Q are computed; the mirror tile (Q, P) receives the transpose, so A stays EXACTLY symmetric
   // from step to step (two independent products Q_P' A[P,Q] Q_Q and Q_Q' A[Q,P] Q_P sum in different orders: symmetric only to
-  // rounding, and k_bj_inner builds its rotations from one triangle) and the step does half the matrix-core work.
+  // rounding, and the inner sweeps build their rotations from one triangle) and the step does half the matrix-core work.
   const int np = sh.nbc / 2, nta = np * (np + 1) / 2, TR = sh.K64 / BJ_W;
   if (tile >= nta + np * TR) return;
   const int *flags = Qflag + (size_t)b * npmax;
@@ -757,7 +554,7 @@ __device__ __forceinline__ void bj_update_job(const BigPsdView &B, unsigned char
     while (Qp * (Qp + 1) / 2 > tile) --Qp;
     while ((Qp + 1) * (Qp + 2) / 2 <= tile) ++Qp;
     const int Pp = tile - Qp * (Qp + 1) / 2;
-    const int2 IJp = bj_pair_sched(Pp, step, sh.nbc, cross), IJq = bj_pair_sched(Qp, step, sh.nbc, cross);
+    const int2 IJp = bj_pair_sched(Pp, step, sh.nbc), IJq = bj_pair_sched(Qp, step, sh.nbc);
     const int fP = flags[Pp], fQ = flags[Qp];
     real left = 0; // largest |entry| written at (row, column) with row != column, both below k (the mirror entry is the same number)
     auto seen = [&](int gi, int gj, real v) {
@@ -825,7 +622,7 @@ __device__ __forceinline__ void bj_update_job(const BigPsdView &B, unsigned char
   tile -= nta;
   const int Qp = tile / TR, r0 = (tile % TR) * BJ_W;
   if (!flags[Qp]) return;
-  const int2 IJq = bj_pair_sched(Qp, step, sh.nbc, cross);
+  const int2 IJq = bj_pair_sched(Qp, step, sh.nbc);
 #pragma unroll 4
   for (int e = tid; e < BJ_W * BJ_W; e += BJ_UPD_THREADS) {
     const int i = e & (BJ_W - 1), kk = e >> 6;
@@ -842,24 +639,9 @@ __device__ __forceinline__ void bj_update_job(const BigPsdView &B, unsigned char
 }
 
 
-__global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_update(BigPsdView B, const real *__restrict__ Qbuf, const real *__restrict__ Sbuf,
-                                                          const int *__restrict__ Qflag, int npmax, int arg, int cross) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char bj_smem[];
-  const int slot = arg & 1, step = arg >> 1;
-  const int b = blockIdx.y, tid = threadIdx.x;
-  BigPsdCtl *ctl = B.ctl + b;
-  const int done = ctl->done, kraw = ctl->kraw, cur = ctl->cur[slot];
-  const BlockShape sh = bp_shape_raw(kraw);
-  const bool active = !done && step < bj_outer_steps(sh.nbc, cross);
-  if (blockIdx.x == 0 && tid == 0) ctl->cur[slot ^ 1] = active ? cur ^ 1 : cur;
-  if (!active) return;
-  const size_t ld = B.ld, mat = (size_t)b * ld * ld;
-  bj_update_job(B, bj_smem, Qbuf, Sbuf, Qflag, npmax, b, blockIdx.x, step, cross, sh, (cur ? B.A1 : B.A) + mat, (cur ? B.A : B.A1) + mat, B.V + mat);
-}
-
-// ---- the fused step (round 4; VERDICT r3 item 2: "overlap outer step k+1's k_bj_inner with step k's k_bj_update").
+// ---- the fused step (round 4; VERDICT r3 item 2: overlap outer step k + 1's inner sweeps with step k's update).
 // The inner sweep is one workgroup per pair of block columns (16 workgroups for a 1024 x 1024 block) and a chain of 32 dependent
-// steps: 40 us in which the rest of the chip idles; the update is 14 us of the whole chip.  As two launches they add up.  This launch
+// steps: 40 us in which the rest of the chip idles; the update is 14 us of the whole chip.  As two launches they added up.  This launch
 // does both: workgroups [0, npmax) run the inner sweep of step k + 1, the others the update of step k.  The inner sweep of step k + 1
 // needs A as the update of step k leaves it -- only the 64 x 64 diagonal subproblem of ITS pair (I', J'), which it forms itself from
 // what the update reads (the matrix before step k, Q and S' of step k's pairs): the quadrants [I', I'] and [J', J'] are pieces of the
@@ -869,18 +651,13 @@ __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_update(BigPsdView B, cons
 // Q / S' / flags are double-buffered by launch (the update of step k reads step k's while the inner sweep writes step k + 1's).
 // The last launch of a sweep runs the FIRST inner sweep of the next sweep before k_bp_sweep_end has closed this one (its
 // off-diagonal maximum goes to the other parity slot of the control record); if the block turns out converged the work is dropped.
-static_assert(BJ_UPD_THREADS == BJ_UPD_THREADS_MAX && BJ_INNER_LAUNCH == BJ_UPD_THREADS_MAX, "bj_inner_sweep_cross lays its roles out over a 1024-thread workgroup");
 struct BjFusedArgs {
-  int slot;        // launch parity of the control record's `cur` (as `arg & 1` of the two-launch form)
+  int slot;        // launch parity of the control record's `cur`
   int do_update;   // 0: the first launch of a projection (inner sweep of step 0 only)
   int upd_step;    // outer step the update workgroups apply
   int inn_step;    // outer step of the inner sweep
   int next_sweep;  // inner sweep belongs to the sweep after the current one (inn_step == 0 of it)
   int qin, qout;   // which of the two Q / S' / flag buffers the update reads / the inner sweep writes
-  int cross;
-  int scan;        // the last update of a block's sweep records the largest off-diagonal entry it writes (no k_bp_offscan launch)
-  int flat;        // inner sweep's prologue with ONE level of global loads (0: rounds 4-5's three levels; A/B measurements)
-  int one_d;       // one-dimensional grid, inner-sweep workgroups of all blocks first (0: x = job, y = block; A/B measurements)
 };
 
 __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_fused(BigPsdView B, real *Qbuf2, real *Sbuf2, int *Qflag2, int npmax, BjFusedArgs F) {
@@ -888,13 +665,10 @@ __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_fused(BigPsdView B, real 
   // One-dimensional grid (round 6): the inner-sweep workgroups of ALL blocks first, then the update workgroups.  Workgroups are handed
   // out in the order of their index and one fits a CU (135 KB of LDS); with (x = job, y = block) the inner sweeps of the later blocks
   // -- the launch's critical path, ~40 us -- queued behind the ~11 us update jobs of the earlier ones whenever a launch has more
-  // workgroups than the chip has CUs (16 blocks of order 200: 480; 4 of 512: 432).  bx: the job index of the old x dimension.
+  // workgroups than the chip has CUs (16 blocks of order 200: 480; 4 of 512: 432).  bx: the job within block b (inner sweeps first).
   const int n_inner = B.nbig * npmax, tid = threadIdx.x;
   int b, bx;
-  if (!F.one_d) {
-    b = blockIdx.y;
-    bx = blockIdx.x;
-  } else if ((int)blockIdx.x < n_inner) {
+  if ((int)blockIdx.x < n_inner) {
     b = (int)blockIdx.x / npmax;
     bx = (int)blockIdx.x - b * npmax;
   } else {
@@ -905,7 +679,7 @@ __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_fused(BigPsdView B, real 
   BigPsdCtl *ctl = B.ctl + b;
   const int done = ctl->done, kraw = ctl->kraw, cur = ctl->cur[F.slot];
   const BlockShape sh = bp_shape_raw(kraw);
-  const int ost = bj_outer_steps(sh.nbc, F.cross);
+  const int ost = sh.nbc; // outer steps of a sweep of THIS block: the within pass, then the nbc - 1 tournament steps
   const bool upd_active = F.do_update && !done && F.upd_step < ost;
   const size_t ld = B.ld, mat = (size_t)b * ld * ld;
   const real *Aold = (cur ? B.A1 : B.A) + mat;
@@ -916,16 +690,15 @@ __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_fused(BigPsdView B, real 
     if (!F.do_update) return;
     if (bx == npmax && tid == 0) ctl->cur[F.slot ^ 1] = upd_active ? cur ^ 1 : cur;
     if (!upd_active) return;
-    bj_update_job(B, bj_smem, Qin, Sin, Fin, npmax, b, bx - npmax, F.upd_step, F.cross, sh, Aold, (cur ? B.A : B.A1) + mat, B.V + mat,
-                  F.scan && F.upd_step == ost - 1 ? &ctl->left_bits : nullptr); // the last update of THIS block's sweep looks at what it leaves
+    bj_update_job(B, bj_smem, Qin, Sin, Fin, npmax, b, bx - npmax, F.upd_step, sh, Aold, (cur ? B.A : B.A1) + mat, B.V + mat,
+                  F.upd_step == ost - 1 ? &ctl->left_bits : nullptr); // the last update of THIS block's sweep looks at what it leaves
     return;
   }
   // ---- inner sweep of step inn_step on the matrix as the update of this launch leaves it
   const int pi = bx;
   if (done || pi >= sh.nbc / 2 || (!F.next_sweep && F.inn_step >= ost)) return;
   const real thr = ctl->thr;
-  const int2 IJ = bj_pair_sched(pi, F.inn_step, sh.nbc, F.cross);
-  const int kind = !F.cross ? 0 : (F.inn_step == 0 ? 1 : 2);
+  const int2 IJ = bj_pair_sched(pi, F.inn_step, sh.nbc);
   real *S = reinterpret_cast<real *>(bj_smem);
   const int nthr = BJ_UPD_THREADS;
   if (!upd_active) { // (a smaller block whose sweep is over, or the first launch) the matrix is not changing under this launch
@@ -937,7 +710,7 @@ __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_fused(BigPsdView B, real 
     __shared__ int s_prev[4]; // pair and half (0: it was the pair's I, 1: its J) of I' and of J' in step upd_step
     const int np = sh.nbc / 2;
     if (tid < np) {
-      const int2 pr = bj_pair_sched(tid, F.upd_step, sh.nbc, F.cross);
+      const int2 pr = bj_pair_sched(tid, F.upd_step, sh.nbc);
       if (pr.x == IJ.x || pr.y == IJ.x) { s_prev[0] = tid; s_prev[1] = pr.y == IJ.x; }
       if (pr.x == IJ.y || pr.y == IJ.y) { s_prev[2] = tid; s_prev[3] = pr.y == IJ.y; }
     }
@@ -945,139 +718,87 @@ __global__ __launch_bounds__(BJ_UPD_THREADS) void k_bj_fused(BigPsdView B, real 
     const int PI = s_prev[0], hI = s_prev[1], PJ = s_prev[2], hJ = s_prev[3];
     const int *flags = Fin + (size_t)b * npmax;
     const real *Qb = Qin + (size_t)b * npmax * BJ_W * BJ_W, *Sb = Sin + (size_t)b * npmax * BJ_W * BJ_W;
-    const int2 prI = bj_pair_sched(PI, F.upd_step, sh.nbc, F.cross), prJ = bj_pair_sched(PJ, F.upd_step, sh.nbc, F.cross);
-    if (F.flat) {
-      // Round 6: ONE level of global loads.  Everything the subproblem is made of is asked for at once -- both candidates of every entry
-      // (S' / Q of the pairs of step k, valid memory whether or not they rotated, and A itself) beside the two flags that pick between
-      // them -- and selected when it is all here.  (Round 4's form below: flags, then the diagonal quadrants, then the tile and the Q
-      // columns, each level waiting for the one before -- three far round trips on the critical path of every launch.)
-      static_assert(BJ_UPD_THREADS == BJ_B * BJ_B, "flat prologue: one entry per quadrant and lane");
-      const int x = tid & (BJ_B - 1), y = tid >> 5;
-      const int fI = flags[PI], fJ = flags[PJ];
-      const size_t tile = (size_t)BJ_W * BJ_W;
-      auto sprime = [&](int P, int rr, int cc) -> real { return Sb[(size_t)P * tile + cc * BJ_W + rr]; };
-      auto aentry = [&](int2 pr, int rr, int cc) -> real { return Aold[(size_t)bj_gidx(pr, cc) * ld + bj_gidx(pr, rr)]; };
-      const real dIs = sprime(PI, hI * BJ_B + x, hI * BJ_B + y), dIa = aentry(prI, hI * BJ_B + x, hI * BJ_B + y);
-      const real dJs = sprime(PJ, hJ * BJ_B + x, hJ * BJ_B + y), dJa = aentry(prJ, hJ * BJ_B + x, hJ * BJ_B + y);
-      const bool swap = PI > PJ;
-      const int Pa = swap ? PJ : PI, Pb = swap ? PI : PJ, ha = swap ? hJ : hI, hb = swap ? hI : hJ;
-      const int2 pra = swap ? prJ : prI, prb = swap ? prI : prJ;
-      real cs_ = 0, ca_ = 0, xv[4] = {0, 0, 0, 0}, qv[2] = {0, 0}, pv[2] = {0, 0};
-      if (PI == PJ) { // (uniform) I' and J' sat in ONE pair of step k: the quadrant is a piece of that pair's diagonal tile too
-        cs_ = sprime(PI, hI * BJ_B + x, hJ * BJ_B + y);
-        ca_ = aentry(prI, hI * BJ_B + x, hJ * BJ_B + y);
-      } else {
-        ca_ = Aold[(size_t)bj_gidx(IJ, BJ_B + y) * ld + bj_gidx(IJ, x)]; // neither pair rotated: the update copies the tile
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), kk = e >> 6;
-          xv[t] = Aold[(size_t)bj_gidx(prb, kk) * ld + bj_gidx(pra, i)];
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), j = e >> 6;
-          qv[t] = Qb[(size_t)Pb * tile + (hb * BJ_B + j) * BJ_W + i];
-          pv[t] = Qb[(size_t)Pa * tile + (ha * BJ_B + j) * BJ_W + i];
-        }
-      }
-      S[x * BJ_ILD + y] = fI ? dIs : dIa;
-      S[(BJ_B + x) * BJ_ILD + BJ_B + y] = fJ ? dJs : dJa;
-      if (PI == PJ || (!fI && !fJ)) {
-        const real v = PI == PJ ? (fI ? cs_ : ca_) : ca_;
-        S[x * BJ_ILD + BJ_B + y] = v;
-        S[(BJ_B + y) * BJ_ILD + x] = v;
-      } else {
-        // the tile (Pa <= Pb) as bj_update_job forms it: O = Q_Pa' A[Pa, Pb] Q_Pb, of which the rows of half ha and the columns of half hb
-        const int fa = swap ? fJ : fI, fb = swap ? fI : fJ;
-        real *xs = S + BJ_W * BJ_ILD; // scratch behind S (see below)
-        real *qq = xs + BJ_W * BJ_LD, *qp = qq + BJ_B * BJ_LD, *ts = qp + BJ_B * BJ_LD, *out = ts + BJ_B * BJ_LD;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), kk = e >> 6;
-          xs[i * BJ_LD + kk] = xv[t];
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), j = e >> 6;
-          qq[j * BJ_LD + i] = fb ? qv[t] : (i == hb * BJ_B + j ? (real)1 : (real)0);
-          qp[j * BJ_LD + i] = fa ? pv[t] : (i == ha * BJ_B + j ? (real)1 : (real)0);
-        }
-        __syncthreads();
-        bj_gemm_part(xs, qq, ts, 4, 2, tid, nthr);  // T[:, hb half] = X Q_Pb[:, hb half]
-        __syncthreads();
-        bj_gemm_part(qp, ts, out, 2, 2, tid, nthr); // O[ha half, hb half] = Q_Pa[:, ha half]' T
-        __syncthreads();
-        const real v = out[y * BJ_LD + x]; // O[i = x][j = y]: row x of half ha, column y of half hb
-        const int xx = swap ? y : x, yy = swap ? x : y; // xx: index in I', yy: index in J'
-        S[xx * BJ_ILD + BJ_B + yy] = v;
-        S[(BJ_B + yy) * BJ_ILD + xx] = v;
-      }
-    } else {
+    const int2 prI = bj_pair_sched(PI, F.upd_step, sh.nbc), prJ = bj_pair_sched(PJ, F.upd_step, sh.nbc);
+    // ONE level of global loads.  Everything the subproblem is made of is asked for at once -- both candidates of every entry (S' / Q of
+    // the pairs of step k, valid memory whether or not they rotated, and A itself) beside the two flags that pick between them -- and
+    // selected when it is all here.  (Asked for level by level -- flags, then the diagonal quadrants, then the tile and the Q columns --
+    // it was three far round trips on the critical path of every launch.)
+    static_assert(BJ_UPD_THREADS == BJ_B * BJ_B, "k_bj_fused prologue: one entry per quadrant and lane");
+    const int x = tid & (BJ_B - 1), y = tid >> 5;
     const int fI = flags[PI], fJ = flags[PJ];
-    // entry (hr * 32 + x, hc * 32 + y) of the diagonal tile of step-k pair P after the update: S' of the pair, or A itself if it did not rotate
-    auto diag = [&](int P, int2 pr, int f, int rr, int cc) -> real {
-      return f ? Sb[(size_t)P * BJ_W * BJ_W + cc * BJ_W + rr] : Aold[(size_t)bj_gidx(pr, cc) * ld + bj_gidx(pr, rr)];
-    };
-    for (int e = tid; e < 2 * BJ_B * BJ_B; e += nthr) { // quadrants [I', I'] and [J', J']
-      const int x = e & (BJ_B - 1), y = (e >> 5) & (BJ_B - 1), which = e >> 10;
-      if (which == 0) S[x * BJ_ILD + y] = diag(PI, prI, fI, hI * BJ_B + x, hI * BJ_B + y);
-      else S[(BJ_B + x) * BJ_ILD + BJ_B + y] = diag(PJ, prJ, fJ, hJ * BJ_B + x, hJ * BJ_B + y);
+    const size_t tile = (size_t)BJ_W * BJ_W;
+    auto sprime = [&](int P, int rr, int cc) -> real { return Sb[(size_t)P * tile + cc * BJ_W + rr]; };
+    auto aentry = [&](int2 pr, int rr, int cc) -> real { return Aold[(size_t)bj_gidx(pr, cc) * ld + bj_gidx(pr, rr)]; };
+    const real dIs = sprime(PI, hI * BJ_B + x, hI * BJ_B + y), dIa = aentry(prI, hI * BJ_B + x, hI * BJ_B + y);
+    const real dJs = sprime(PJ, hJ * BJ_B + x, hJ * BJ_B + y), dJa = aentry(prJ, hJ * BJ_B + x, hJ * BJ_B + y);
+    const bool swap = PI > PJ;
+    const int Pa = swap ? PJ : PI, Pb = swap ? PI : PJ, ha = swap ? hJ : hI, hb = swap ? hI : hJ;
+    const int2 pra = swap ? prJ : prI, prb = swap ? prI : prJ;
+    real cs_ = 0, ca_ = 0, xv[4] = {0, 0, 0, 0}, qv[2] = {0, 0}, pv[2] = {0, 0};
+    if (PI == PJ) { // (uniform) I' and J' sat in ONE pair of step k: the quadrant is a piece of that pair's diagonal tile too
+      cs_ = sprime(PI, hI * BJ_B + x, hJ * BJ_B + y);
+      ca_ = aentry(prI, hI * BJ_B + x, hJ * BJ_B + y);
+    } else {
+      ca_ = Aold[(size_t)bj_gidx(IJ, BJ_B + y) * ld + bj_gidx(IJ, x)]; // neither pair rotated: the update copies the tile
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), kk = e >> 6;
+        xv[t] = Aold[(size_t)bj_gidx(prb, kk) * ld + bj_gidx(pra, i)];
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), j = e >> 6;
+        qv[t] = Qb[(size_t)Pb * tile + (hb * BJ_B + j) * BJ_W + i];
+        pv[t] = Qb[(size_t)Pa * tile + (ha * BJ_B + j) * BJ_W + i];
+      }
     }
-    if (PI == PJ) { // I' and J' sat in ONE pair of step k: the quadrant is a piece of that pair's diagonal tile too
-      for (int e = tid; e < BJ_B * BJ_B; e += nthr) {
-        const int x = e & (BJ_B - 1), y = e >> 5;
-        const real v = diag(PI, prI, fI, hI * BJ_B + x, hJ * BJ_B + y);
-        S[x * BJ_ILD + BJ_B + y] = v;
-        S[(BJ_B + y) * BJ_ILD + x] = v;
-      }
-    } else if (!fI && !fJ) { // neither pair rotated: the update copies the tile
-      for (int e = tid; e < BJ_B * BJ_B; e += nthr) {
-        const int x = e & (BJ_B - 1), y = e >> 5;
-        const real v = Aold[(size_t)bj_gidx(IJ, BJ_B + y) * ld + bj_gidx(IJ, x)];
-        S[x * BJ_ILD + BJ_B + y] = v;
-        S[(BJ_B + y) * BJ_ILD + x] = v;
-      }
+    S[x * BJ_ILD + y] = fI ? dIs : dIa;
+    S[(BJ_B + x) * BJ_ILD + BJ_B + y] = fJ ? dJs : dJa;
+    if (PI == PJ || (!fI && !fJ)) {
+      const real v = PI == PJ ? (fI ? cs_ : ca_) : ca_;
+      S[x * BJ_ILD + BJ_B + y] = v;
+      S[(BJ_B + y) * BJ_ILD + x] = v;
     } else {
       // the tile (Pa <= Pb) as bj_update_job forms it: O = Q_Pa' A[Pa, Pb] Q_Pb, of which the rows of half ha and the columns of half hb
-      const bool swap = PI > PJ;
-      const int Pa = swap ? PJ : PI, Pb = swap ? PI : PJ, ha = swap ? hJ : hI, hb = swap ? hI : hJ, fa = swap ? fJ : fI, fb = swap ? fI : fJ;
-      const int2 pra = swap ? prJ : prI, prb = swap ? prI : prJ;
+      const int fa = swap ? fJ : fI, fb = swap ? fI : fJ;
       real *xs = S + BJ_W * BJ_ILD; // scratch behind S, over its second copy, Q and the rotation tables (which the sweep sets up afterwards): ends at 134 656 B
       static_assert((size_t)(BJ_W * BJ_ILD + BJ_W * BJ_LD + 4 * BJ_B * BJ_LD) * sizeof(real) <= BJ_UPDATE_LDS, "k_bj_fused: prologue scratch");
       real *qq = xs + BJ_W * BJ_LD, *qp = qq + BJ_B * BJ_LD, *ts = qp + BJ_B * BJ_LD, *out = ts + BJ_B * BJ_LD;
-      for (int e = tid; e < BJ_W * BJ_W; e += nthr) {
-        const int i = e & (BJ_W - 1), kk = e >> 6;
-        xs[i * BJ_LD + kk] = Aold[(size_t)bj_gidx(prb, kk) * ld + bj_gidx(pra, i)];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), kk = e >> 6;
+        xs[i * BJ_LD + kk] = xv[t];
       }
-      for (int e = tid; e < BJ_W * BJ_B; e += nthr) { // 32 columns of each Q (identity where the pair did not rotate)
-        const int i = e & (BJ_W - 1), j = e >> 6;
-        qq[j * BJ_LD + i] = fb ? Qb[(size_t)Pb * BJ_W * BJ_W + (hb * BJ_B + j) * BJ_W + i] : (i == hb * BJ_B + j ? (real)1 : (real)0);
-        qp[j * BJ_LD + i] = fa ? Qb[(size_t)Pa * BJ_W * BJ_W + (ha * BJ_B + j) * BJ_W + i] : (i == ha * BJ_B + j ? (real)1 : (real)0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int e = tid + t * BJ_UPD_THREADS, i = e & (BJ_W - 1), j = e >> 6;
+        qq[j * BJ_LD + i] = fb ? qv[t] : (i == hb * BJ_B + j ? (real)1 : (real)0);
+        qp[j * BJ_LD + i] = fa ? pv[t] : (i == ha * BJ_B + j ? (real)1 : (real)0);
       }
       __syncthreads();
       bj_gemm_part(xs, qq, ts, 4, 2, tid, nthr);  // T[:, hb half] = X Q_Pb[:, hb half]
       __syncthreads();
       bj_gemm_part(qp, ts, out, 2, 2, tid, nthr); // O[ha half, hb half] = Q_Pa[:, ha half]' T
       __syncthreads();
-      for (int e = tid; e < BJ_B * BJ_B; e += nthr) {
-        const int i = e & (BJ_B - 1), j = e >> 5; // O[i][j] at out[j * BJ_LD + i]: row i of half ha, column j of half hb
-        const real v = out[j * BJ_LD + i];
-        const int x = swap ? j : i, y = swap ? i : j; // x: index in I', y: index in J'
-        S[x * BJ_ILD + BJ_B + y] = v;
-        S[(BJ_B + y) * BJ_ILD + x] = v;
-      }
-    }
+      const real v = out[y * BJ_LD + x]; // O[i = x][j = y]: row x of half ha, column y of half hb
+      const int xx = swap ? y : x, yy = swap ? x : y; // xx: index in I', yy: index in J'
+      S[xx * BJ_ILD + BJ_B + yy] = v;
+      S[(BJ_B + yy) * BJ_ILD + xx] = v;
     }
   }
   __syncthreads();
   const size_t slot_q = (size_t)b * npmax + pi;
-  bj_inner_sweep(bj_smem, IJ, kind, sh.k, thr, ctl, (ctl->sweeps + (F.next_sweep ? 1 : 0)) & 1, Qbuf2 + F.qout * qsz + slot_q * BJ_W * BJ_W,
-                 Sbuf2 + F.qout * qsz + slot_q * BJ_W * BJ_W, Qflag2 + F.qout * fsz + slot_q);
+  const int offslot = (ctl->sweeps + (F.next_sweep ? 1 : 0)) & 1;
+  real *Qg = Qbuf2 + F.qout * qsz + slot_q * BJ_W * BJ_W, *Sg = Sbuf2 + F.qout * qsz + slot_q * BJ_W * BJ_W;
+  int *flag = Qflag2 + F.qout * fsz + slot_q;
+  if (F.inn_step == 0) bj_inner_sweep_within(bj_smem, IJ, sh.k, thr, ctl, offslot, Qg, Sg, flag);
+  else bj_inner_sweep_cross(bj_smem, IJ, sh.k, thr, ctl, offslot, Qg, Sg, flag);
 }
 
-// closes a sweep for every block (one wave, a lane per block); remaining[0] = blocks still iterating.  scanned: left_bits holds the largest
-// off-diagonal entry of the matrix as this sweep left it
-__global__ __launch_bounds__(SCSAMD_WAVE) void k_bp_sweep_end(BigPsdView B, int *status, int *remaining, int scanned) {
+// closes a sweep for every block (one wave, a lane per block); remaining[0] = blocks still iterating.  left_bits: the largest off-diagonal
+// entry of the matrix as this sweep left it (bj_update_job); at or below the threshold, the next sweep would rotate nothing and is
+// not run (profiles/r6_psd_big.md).
+__global__ __launch_bounds__(SCSAMD_WAVE) void k_bp_sweep_end(BigPsdView B, int *status, int *remaining) {
   int rem = 0, worked = 0;
   for (int b = threadIdx.x; b < B.nbig; b += SCSAMD_WAVE) {
     BigPsdCtl *c = B.ctl + b;
@@ -1085,7 +806,7 @@ __global__ __launch_bounds__(SCSAMD_WAVE) void k_bp_sweep_end(BigPsdView B, int 
     worked = 1;
     const int par = c->sweeps & 1;
     c->sweeps += 1;
-    const bool nothing_left = scanned && bp_from_bits(c->left_bits) <= c->thr; // the next sweep would rotate nothing
+    const bool nothing_left = bp_from_bits(c->left_bits) <= c->thr; // the next sweep would rotate nothing
     c->left_bits = 0ull;
     if (bp_from_bits(c->offmax_bits[par]) <= c->thr || nothing_left) {
       c->done = 1;
@@ -1103,36 +824,6 @@ __global__ __launch_bounds__(SCSAMD_WAVE) void k_bp_sweep_end(BigPsdView B, int 
     remaining[0] = rem;
     remaining[1] += worked; // sweeps of this projection in which some block still iterated (the host sizes its next batch from it)
   }
-}
-
-// The largest off-diagonal entry of every block that is still iterating, in the matrix as the sweep just run leaves it (round 6).
-// The iteration ends with a sweep that meets no entry above the threshold, i.e. one that rotates nothing: whether the NEXT sweep
-// would be that one can be read off the matrix in one pass (8 MB at order 1024) instead of being found out by running it (32
-// launches of ~20 us there, 8 at order 256: 5 % of a cold projection, a third to a half of a warm-started one of 2 - 3 sweeps).
-// Same rule (|a_pq| > thr rotates, both indices below k), same final matrix bit for bit; both triangles are read, so whichever mirror
-// entry a rotation would have looked at is covered.  slot: parity of the next launch (ctl.cur), as k_bp_scale.
-// The fused step does this inside the last update of the sweep (bj_update_job's left_bits: that launch rewrites the whole matrix anyway);
-// this kernel serves the forms that do not come through there (two-launch step, single-column steps, option psd_offscan = 2).
-// (Closing the sweep from the workgroup that finishes last -- a ticket behind a fence -- instead of k_bp_sweep_end's launch was
-// measured and dropped: an agent-scope fence per workgroup writes the XCD's L2 back; 100 x 32: 1.73 vs 1.35 ms per projection.)
-__global__ __launch_bounds__(BP_THREADS) void k_bp_offscan(BigPsdView B, int slot) {
-  __shared__ real red[BP_THREADS / SCSAMD_WAVE];
-  const int b = blockIdx.y;
-  BigPsdCtl *c = B.ctl + b;
-  if (c->done) return;
-  const BlockShape s = bp_shape_raw(c->kraw);
-  const real *A = (c->cur[slot] ? B.A1 : B.A) + (size_t)b * B.ld * B.ld;
-  real mx = 0;
-  for (int j = blockIdx.x; j < s.k; j += gridDim.x) {
-    const real *col = A + (size_t)j * B.ld;
-    for (int i = threadIdx.x; i < s.k; i += BP_THREADS) {
-      const real a = absval(col[i]);
-      if (i != j && a > mx) mx = a;
-    }
-  }
-  mx = block_max(mx, red);
-  // (the relaxed read may be behind the other workgroups' maxima, i.e. too small: a needless atomic then, never a missing one)
-  if (threadIdx.x == 0 && mx > bp_from_bits(__hip_atomic_load(&c->left_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) atomicMax(&c->left_bits, bp_bits(mx));
 }
 
 // W = V diag(sqrt(max(lambda, 0)))   (cones.c:1036-1044), in place
@@ -1383,17 +1074,11 @@ struct BigPsd {
   PinnedBuf<int> hrem;       // host copy of `remaining`
   long long sweeps_total = 0, projections = 0;
   bool warm_ok = true;
-  bool blocked = true;       // tournament over 32-wide block columns with MFMA updates (k_bj_*); false: single columns (k_bp_step)
+  bool debug = false;        // option `debug`, as it stood when the workspace was created
   int sweeps_hint[2] = {0, 0}; // sweeps the previous projection of the same kind ([0] cold start, [1] warm start) needed: that many minus one
                              // are enqueued before the first read-back (a cold projection's ~10 must not size the next warm one's batch)
-  bool fused = true;         // blocked: one launch per outer step (k_bj_fused) instead of k_bj_inner + k_bj_update
   DevBuf<real> normpart;     // k_bp_norm_part's partial sums
-  bool offscan_fold = true;  // the scan inside the last update of a sweep (fused step) instead of k_bp_offscan's launch
-  bool flat_prologue = true; // k_bj_fused: the inner sweep's subproblem from one level of global loads
-  bool grid_1d = true;       // k_bj_fused: one-dimensional grid, inner-sweep workgroups of all blocks first
-  bool offscan = true;       // a pass over the matrix after every sweep decides whether another sweep would rotate anything (k_bp_offscan)
-  bool cross = true;         // blocked: every index pair once per sweep (within pass + cross-pair tournament steps), see bj_pair_sched
-  DevBuf<real> Qbuf, Sbuf;   // blocked: per (block, block-column pair) the 64 x 64 factor Q and rotated subproblem S'
+  DevBuf<real> Qbuf, Sbuf;   // per (block, block-column pair) the 64 x 64 factor Q and rotated subproblem S'
   DevBuf<int> Qflag;         // ... and whether the pair's inner sweep rotated at all
   void reset_warm_start() { calls = 0; have_basis = false; sweeps_hint[0] = sweeps_hint[1] = 0; }
 
@@ -1410,36 +1095,19 @@ struct BigPsd {
     }
     nbig = (int)ids.size();
     if (!nbig) return;
-    blocked = true;
-    if (const char *e = opt_get("psd_blocked")) blocked = atoi(e) != 0; // 0: the single-column steps of round 2 (A/B measurements)
-    ld = blocked ? (kmax + BJ_W - 1) / BJ_W * BJ_W : (kmax + 1) & ~1;
+    ld = (kmax + BJ_W - 1) / BJ_W * BJ_W;
     normpart.alloc((size_t)nbig * BP_NORM_G);
-    offscan_fold = true;
-    if (const char *e = opt_get("psd_offscan")) offscan_fold = atoi(e) != 2; // 2: the scan as a launch of its own (A/B measurements)
-    flat_prologue = true;
-    if (const char *e = opt_get("psd_prologue")) flat_prologue = atoi(e) != 0; // 0: rounds 4-5's three dependent levels of loads (A/B measurements)
-    grid_1d = true;
-    if (const char *e = opt_get("psd_grid")) grid_1d = atoi(e) != 0; // 0: (job, block) grid of rounds 4-5 (A/B measurements)
-    offscan = true;
-    if (const char *e = opt_get("psd_offscan")) offscan = atoi(e) != 0; // 0: rounds 2-5's closing sweep that rotates nothing (A/B measurements)
-    cross = true;
-    if (const char *e = opt_get("psd_cross")) cross = atoi(e) != 0; // 0: full 63-step sweeps of every block-column pair (first form of round 3)
-    if (blocked) {
-      const size_t npmax = (size_t)ld / BJ_W;
-      fused = true;
-      if (const char *e = opt_get("psd_fused")) fused = atoi(e) != 0; // 0: inner sweep and update as two launches per outer step (A/B measurements)
-      Qbuf.alloc((size_t)2 * nbig * npmax * BJ_W * BJ_W); // two generations (k_bj_fused)
-      Sbuf.alloc((size_t)2 * nbig * npmax * BJ_W * BJ_W);
-      Qflag.alloc((size_t)2 * nbig * npmax);
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bj_fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BJ_UPDATE_LDS));
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bj_inner), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BJ_INNER_LDS));
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bj_update), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BJ_UPDATE_LDS));
-    }
+    const size_t npmax = (size_t)ld / BJ_W;
+    Qbuf.alloc((size_t)2 * nbig * npmax * BJ_W * BJ_W); // two generations (k_bj_fused)
+    Sbuf.alloc((size_t)2 * nbig * npmax * BJ_W * BJ_W);
+    Qflag.alloc((size_t)2 * nbig * npmax);
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bj_fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BJ_UPDATE_LDS));
     id.alloc(ids.size());
     id.upload(ids.data(), ids.size(), st);
     A.alloc((size_t)nbig * ld * ld);
     V.alloc((size_t)nbig * ld * ld);
     warm_ok = !opt_get("psd_cold");
+    debug = opt_get("debug") != nullptr;
     if (warm_ok) Vp.alloc((size_t)nbig * ld * ld);
     Tm.alloc((size_t)nbig * ld * ld); // T of the warm start, then the second copy of A during the sweeps
     have_basis = false;
@@ -1456,15 +1124,13 @@ struct BigPsd {
     BigPsdView B{nbig, ld, id.p, psd_off, psd_k, A.p, V.p, Tm.p, ctl.p};
     const long long elems = (long long)ld * ld;
     const int g_elem = (int)std::min<long long>((elems + BP_THREADS - 1) / BP_THREADS, 2048);
-    const int np_max = ld / 2, TPm = (np_max + BP_TILE - 1) / BP_TILE;
-    const int g_step = TPm * TPm + ((np_max + BP_VPAIRS - 1) / BP_VPAIRS) * ((ld + BP_VROWS - 1) / BP_VROWS); // tiles of the largest block
     // warm start (as in the LDS kernel): iterate on A' = Vp' A Vp from V = Vp, the eigenbasis of the previous projection
     // of the same block; a cold restart every PSD_WARM_RESET calls bounds the orthogonality drift of the carried basis
     const bool warm = warm_ok && have_basis && (calls % PSD_WARM_RESET) != 0;
     ++calls;
     const size_t mat_bytes = (size_t)nbig * ld * ld * sizeof(real);
     hipLaunchKernelGGL(k_bp_set_kraw, dim3((nbig + 63) / 64), dim3(64), 0, st, B, remaining.p);
-    hipLaunchKernelGGL(k_bp_unpack, dim3(g_elem, nbig), dim3(BP_THREADS), 0, st, B, x, warm ? 0 : 1, blocked ? 1 : 0);
+    hipLaunchKernelGGL(k_bp_unpack, dim3(g_elem, nbig), dim3(BP_THREADS), 0, st, B, x, warm ? 0 : 1);
     if (warm) {
       const long long T32 = (ld + 31) / 32;
       const int g_mm = (int)std::min<long long>((T32 * T32 + 3) / 4, 8192); // one 32 x 32 tile per wave
@@ -1478,52 +1144,35 @@ struct BigPsd {
     int *h_rem = hrem.p; // (pinned: the read-back of two ints into pageable memory went through the runtime's staging copy)
     h_rem[0] = nbig;
     h_rem[1] = 0;
-    long long qgen = 0;  // fused step: generations of Q / S' / flags written so far
+    long long qgen = 0;  // generations of Q / S' / flags written so far
     bool first_launch = true;
     long long gstep = 0; // launches so far: the copy of A a block is in alternates with the steps IT took (ctl.cur)
     const long long sweeps_before = sweeps_total;
-    const int nbc_max = ld / BJ_B, npmax = ld / BJ_W;
+    const int npmax = ld / BJ_W;
+    const int osteps = ld / BJ_B; // outer steps of a sweep of the largest block: the within pass, then the tournament steps
     const int g_upd = npmax * (npmax + 1) / 2 + npmax * (ld / BJ_W); // A tiles (P <= Q: the mirror tile is written by the same workgroup) + V tiles of the largest block
+    const int g_fused = npmax + g_upd;
     // Sweeps are enqueued in batches: as many as the previous projection of these blocks needed, minus one, before the first
     // read-back, then one at a time (consecutive ADMM iterates need nearly the same count; a block that has converged makes every
     // later launch return at once, as in the PCG loop; the sweep cap of cones.c:1031 is enforced on the device).  One host
     // round trip per sweep cost 50 - 100 us -- a third of a projection of 32 blocks of order 100.
-    const bool scan_in_update = offscan && blocked && fused && offscan_fold; // the fused step's last update of a sweep does the scan
-    const int g_scan = std::max(1, std::min(ld / 2, std::max(ld / 8, 1024 / nbig))); // whole columns per workgroup; ~1024 workgroups in all (order 1024 on 64: 21 us)
     int enq = 0, batch = std::max(1, std::min(sweeps_hint[warm ? 1 : 0] - 1, warm ? 8 : 12)); // (all of them: measured the same, 2.70 vs 2.71 ms at 256 x 8)
     while (h_rem[0] > 0 && enq < PSD_MAX_SWEEPS + 4) {
-     for (int bsw = 0; bsw < batch; ++bsw, ++enq) {
-      if (blocked) {
-        const int osteps = cross ? nbc_max : nbc_max - 1; // cross schedule: the within pass, then the tournament steps
-        if (fused) {
-          const int g_fused = npmax + g_upd;
-          for (int step = 0; step < osteps; ++step, ++gstep) {
-            if (first_launch) { // inner sweep of step 0 of the first sweep; nothing to update yet
-              const BjFusedArgs F0{(int)(gstep & 1), 0, 0, 0, 0, 0, (int)(qgen & 1), cross ? 1 : 0, scan_in_update ? 1 : 0, flat_prologue ? 1 : 0, grid_1d ? 1 : 0};
-              hipLaunchKernelGGL(k_bj_fused, grid_1d ? dim3(npmax * nbig) : dim3(npmax, nbig), dim3(BJ_UPD_THREADS), BJ_UPDATE_LDS, st, B, Qbuf.p, Sbuf.p, Qflag.p, npmax, F0);
-              ++qgen;
-              first_launch = false;
-            }
-            const bool last = step + 1 == osteps;
-            const BjFusedArgs F{(int)(gstep & 1), 1, step, last ? 0 : step + 1, last ? 1 : 0, (int)((qgen - 1) & 1), (int)(qgen & 1), cross ? 1 : 0, scan_in_update ? 1 : 0, flat_prologue ? 1 : 0, grid_1d ? 1 : 0};
-            hipLaunchKernelGGL(k_bj_fused, grid_1d ? dim3(g_fused * nbig) : dim3(g_fused, nbig), dim3(BJ_UPD_THREADS), BJ_UPDATE_LDS, st, B, Qbuf.p, Sbuf.p, Qflag.p, npmax, F);
-            ++qgen;
-          }
-        } else
+      for (int bsw = 0; bsw < batch; ++bsw, ++enq) {
         for (int step = 0; step < osteps; ++step, ++gstep) {
-          const int arg = (int)(gstep & 1) | (step << 1);
-          hipLaunchKernelGGL(k_bj_inner, dim3(npmax, nbig), dim3(BJ_INNER_LAUNCH), BJ_INNER_LDS, st, B, Qbuf.p, Sbuf.p, Qflag.p, npmax, arg,
-                             cross ? 1 : 0);
-          hipLaunchKernelGGL(k_bj_update, dim3(g_upd, nbig), dim3(BJ_UPD_THREADS), BJ_UPDATE_LDS, st, B, (const real *)Qbuf.p,
-                             (const real *)Sbuf.p, (const int *)Qflag.p, npmax, arg, cross ? 1 : 0);
+          if (first_launch) { // inner sweep of step 0 of the first sweep; nothing to update yet
+            const BjFusedArgs F0{(int)(gstep & 1), 0, 0, 0, 0, 0, (int)(qgen & 1)};
+            hipLaunchKernelGGL(k_bj_fused, dim3(npmax * nbig), dim3(BJ_UPD_THREADS), BJ_UPDATE_LDS, st, B, Qbuf.p, Sbuf.p, Qflag.p, npmax, F0);
+            ++qgen;
+            first_launch = false;
+          }
+          const bool last = step + 1 == osteps;
+          const BjFusedArgs F{(int)(gstep & 1), 1, step, last ? 0 : step + 1, last ? 1 : 0, (int)((qgen - 1) & 1), (int)(qgen & 1)};
+          hipLaunchKernelGGL(k_bj_fused, dim3(g_fused * nbig), dim3(BJ_UPD_THREADS), BJ_UPDATE_LDS, st, B, Qbuf.p, Sbuf.p, Qflag.p, npmax, F);
+          ++qgen;
         }
-      } else {
-        for (int step = 0; step < ld - 1; ++step, ++gstep)
-          hipLaunchKernelGGL(k_bp_step, dim3(g_step, nbig), dim3(BP_THREADS), 0, st, B, (int)(gstep & 1) | (step << 1));
+        hipLaunchKernelGGL(k_bp_sweep_end, dim3(1), dim3(SCSAMD_WAVE), 0, st, B, status, remaining.p);
       }
-      if (offscan && !scan_in_update) hipLaunchKernelGGL(k_bp_offscan, dim3(g_scan, nbig), dim3(BP_THREADS), 0, st, B, (int)(gstep & 1));
-      hipLaunchKernelGGL(k_bp_sweep_end, dim3(1), dim3(SCSAMD_WAVE), 0, st, B, status, remaining.p, offscan ? 1 : 0);
-     }
       HIP_CHECK(hipMemcpyAsync(h_rem, remaining.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
       batch = 1;
@@ -1531,7 +1180,6 @@ struct BigPsd {
     sweeps_total += h_rem[1];
     sweeps_hint[warm ? 1 : 0] = h_rem[1];
     ++projections;
-    static const bool debug = opt_get("debug") != nullptr;
     if (debug) fprintf(stderr, "[scs_amd psd_big] projection %lld: %s start, sweeps so far %lld (this one %lld)\n", projections, warm ? "warm" : "cold", sweeps_total, sweeps_total - sweeps_before);
     if (warm_ok) {
       HIP_CHECK(hipMemcpyAsync(Vp.p, V.p, mat_bytes, hipMemcpyDeviceToDevice, st));

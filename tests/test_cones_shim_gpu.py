@@ -276,93 +276,50 @@ def test_lds_kernel_orders_73_to_92_warm_started_match_reference(cone):
     ref._scs_finish_cone(wr)
 
 
-@pytest.mark.parametrize("cone", [dict(s=[100, 131, 300]), dict(s=[257], cs=[70])])
-def test_fused_step_equals_the_two_launch_form(cone, monkeypatch):
-    """Round 4: one launch per outer step of the blocked Jacobi iteration (k_bj_fused: the inner sweep of step k + 1 beside the
-    update of step k, forming its subproblem from pre-update data with the update's own tile products).  The subproblem must have
-    the bits the update writes, so the whole projection must equal the two-launch form's (SCS_AMD_PSD_FUSED=0, read at init) to
-    rounding -- over a cold call and two warm-started ones, for blocks with different numbers of block columns in one launch."""
+# (seed of x0, steps, step size, first seed of the moves): x0 + step size * rep * (standard normal of seed `first seed + rep`)
+@pytest.mark.parametrize("cone,drift", [(dict(s=[100, 150, 97], cs=[60]), (33, 4, 0.02, 40)),
+                                        (dict(s=[100, 131, 300]), (11, 3, 0.05, 12)),
+                                        (dict(s=[257], cs=[70]), (11, 3, 0.05, 12))])
+def test_large_block_iteration_mixed_sizes_cold_and_warm_match_reference(cone, drift):
+    """Several blocks of order > 92 with different numbers of block columns, real and Hermitian, in ONE cone -- so that one launch of
+    the fused step (psd_big.h, k_bj_fused) carries blocks whose sweeps end at different outer steps and converge after different
+    numbers of sweeps -- over a drifting sequence: a cold projection, then warm-started ones.  (a) every projection equals the
+    reference's LAPACK path (src/cones.c:999-1155) on the same input to 1e-11 of scale; (b) a second, fresh workspace fed the same
+    sequence returns the same bits: the iteration's only atomics are maxima, every sum has one owner and a fixed order."""
+    ref = _ref_lib()
     lib = _lib()
+    Tr = ref._scs_types
     m = capi.cone_rows(cone)
-    outs = {}
-    for fused in ("1", "0"):
-        monkeypatch.setenv("SCS_AMD_PSD_FUSED", fused)
+    seed, steps, scale, seed0 = drift
+    x0 = np.random.default_rng(seed).standard_normal(m)
+    seq = [x0 + scale * rep * np.random.default_rng(seed0 + rep).standard_normal(m) for rep in range(steps)]
+    kr = capi.make_cone(cone, Tr)
+    wr = ref._scs_init_cone(C.byref(kr), m)
+    assert wr
+    want = []
+    for x in seq:
+        w = x.copy()
+        assert ref._scs_proj_dual_cone(w.ctypes.data_as(Tr.fp), wr, None, None) == 0
+        want.append(w)
+    ref._scs_finish_cone(wr)
+    runs = []
+    for _ in range(2):
         k = capi.make_cone(cone)
         c = lib._scs_init_cone(C.byref(k), m)
         assert c
         res = []
-        x0 = np.random.default_rng(11).standard_normal(m)
-        for rep in range(3):
-            x = x0 + 0.05 * rep * np.random.default_rng(12 + rep).standard_normal(m)
-            assert lib._scs_proj_dual_cone(x.ctypes.data_as(T.fp), c, None, None) == 0
-            res.append(x)
-        outs[fused] = res
+        for x in seq:
+            got = x.copy()
+            assert lib._scs_proj_dual_cone(got.ctypes.data_as(T.fp), c, None, None) == 0
+            res.append(got)
         lib._scs_finish_cone(c)
-    for a, b in zip(outs["1"], outs["0"]):
-        assert np.abs(a - b).max() <= 1e-12 * max(1.0, np.abs(b).max()), np.abs(a - b).max()
-
-
-@pytest.mark.parametrize("env", [dict(SCS_AMD_PSD_CROSS="0"), dict(SCS_AMD_PSD_CROSS="0", SCS_AMD_PSD_FUSED="0"), dict(SCS_AMD_PSD_BLOCKED="0")])
-def test_measurement_forms_of_the_large_block_iteration_still_project(env, monkeypatch):
-    """The forms kept for A/B measurements -- full 63-step subproblem sweeps (SCS_AMD_PSD_CROSS=0; through the fused step and as two
-    launches) and round 2's single-column steps (SCS_AMD_PSD_BLOCKED=0) -- share the control record, the generic inner sweep and the
-    update with the shipped form: they must still agree with it (different rotation orders: to 1e-10 of scale, not to rounding)."""
-    lib = _lib()
-    cone = dict(s=[100, 150])
-    m = capi.cone_rows(cone)
-    x0 = np.random.default_rng(21).standard_normal(m)
-
-    def run():
-        k = capi.make_cone(cone)
-        c = lib._scs_init_cone(C.byref(k), m)
-        assert c
-        res = []
-        for rep in range(2):
-            x = x0 * (1.0 + 0.1 * rep)
-            assert lib._scs_proj_dual_cone(x.ctypes.data_as(T.fp), c, None, None) == 0
-            res.append(x)
-        lib._scs_finish_cone(c)
-        return res
-
-    want = run()
-    for kk, v in env.items():
-        monkeypatch.setenv(kk, v)
-    got = run()
-    for a, b in zip(got, want):
-        assert np.abs(a - b).max() <= 1e-10 * max(1.0, np.abs(b).max()), (env, np.abs(a - b).max())
-
-
-@pytest.mark.parametrize("env", [dict(SCS_AMD_PSD_OFFSCAN="0"), dict(SCS_AMD_PSD_OFFSCAN="2"), dict(SCS_AMD_PSD_GRID="0"), dict(SCS_AMD_PSD_PROLOGUE="0"),
-                                 dict(SCS_AMD_PSD_OFFSCAN="0", SCS_AMD_PSD_GRID="0", SCS_AMD_PSD_PROLOGUE="0")])
-def test_round_6_forms_of_the_large_block_iteration_change_no_bit(env, monkeypatch):
-    """Round 6 (profiles/r6_psd_big.md): the pass over the matrix that replaces the closing sweep (a sweep that rotates nothing changes
-    nothing), the one-dimensional grid of the fused step (same jobs, another hand-out order) and the one-level prologue of its inner
-    sweep (same entries, asked for at once) are schedules, not arithmetic: against rounds 4-5's forms (options psd_offscan = 0,
-    psd_grid = 0, psd_prologue = 0) every projection -- cold and warm started, real and Hermitian blocks of
-    several sizes in one cone -- must come out bit for bit the same."""
-    lib = _lib()
-    cone = dict(s=[100, 150, 97], cs=[60])
-    m = capi.cone_rows(cone)
-    x0 = np.random.default_rng(33).standard_normal(m)
-
-    def run():
-        k = capi.make_cone(cone)
-        c = lib._scs_init_cone(C.byref(k), m)
-        assert c
-        res = []
-        for rep in range(4):
-            x = x0 + 0.02 * rep * np.random.default_rng(40 + rep).standard_normal(m)
-            assert lib._scs_proj_dual_cone(x.ctypes.data_as(T.fp), c, None, None) == 0
-            res.append(x)
-        lib._scs_finish_cone(c)
-        return res
-
-    want = run()
-    for kk, v in env.items():
-        monkeypatch.setenv(kk, v)
-    got = run()
-    for a, b in zip(got, want):
-        assert np.array_equal(a, b), (env, np.abs(a - b).max())
+        runs.append(res)
+    for rep, (got, w) in enumerate(zip(runs[0], want)):
+        err = np.abs(got - w).max() / max(1.0, np.abs(w).max())
+        print(cone, rep, "error against the reference", err)
+        assert err <= 1e-11, (cone, rep, err)
+    for rep, (a, b2) in enumerate(zip(runs[0], runs[1])):
+        assert np.array_equal(a, b2), (cone, rep, np.abs(a - b2).max())
 
 
 # ---- round 6 (VERDICT r5 weak 1): the pipelined kernel's NB = 2 instantiation (every order 51..72) on hardware ----------------

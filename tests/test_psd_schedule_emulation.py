@@ -1,6 +1,6 @@
 """A numpy restatement of the SCHEDULE of the blocked Jacobi iteration for PSD blocks beyond the LDS path
-(scs_amd/csrc/psd_big.h: `bj_pair`, `bj_pair_sched`, `bj_inner_pair`, `k_bj_inner`, `k_bj_update`) -- test infrastructure, CPU
-only: tile-level, not lane-level.  It pins what the kernels' orchestration relies on:
+(scs_amd/csrc/psd_big.h: `bj_pair`, `bj_pair_sched`, `bj_within_pair` and the cross sweep's pairs, the inner sweeps and
+`bj_update_job` of `k_bj_fused`) -- test infrastructure, CPU only: tile-level, not lane-level.  It pins what the kernels' orchestration relies on:
 
  * the tournament over block columns pairs every two block columns exactly once per sweep and covers all columns in every step;
  * the every-pair-once schedule (a within-block pass, then cross pairs only) rotates every index pair exactly once per sweep;
@@ -22,20 +22,20 @@ def bj_pair(i, step, nbc):
     return (I, J) if I < J else (J, I)
 
 
-def bj_pair_sched(i, ostep, nbc, cross):
-    if not cross:
-        return bj_pair(i, ostep, nbc)
+def bj_pair_sched(i, ostep, nbc):
     return (2 * i, 2 * i + 1) if ostep == 0 else bj_pair(i, ostep - 1, nbc)
 
 
-def bj_inner_pair(i, st, kind):
-    if kind == 2:
-        return i, B + ((i + st) & (B - 1))
-    n, j, off = (B, i & (B // 2 - 1), B if i >= B // 2 else 0) if kind == 1 else (W, i, 0)
+def bj_within_pair(i, st):
+    n, j, off = B, i & (B // 2 - 1), B if i >= B // 2 else 0
     p = 0 if j == 0 else 1 + ((j - 1 + st) % (n - 1))
     q = 1 + ((n - 2 - j + st) % (n - 1))
     p, q = (p, q) if p < q else (q, p)
     return p + off, q + off
+
+
+def bj_cross_pair(i, st):
+    return i, B + ((i + st) & (B - 1))
 
 
 def gidx(IJ):
@@ -58,11 +58,11 @@ def test_every_pair_once_schedule_rotates_every_index_pair_exactly_once_per_swee
     nbc = 6
     seen = {}
     for ostep in range(nbc):  # the within pass, then the nbc - 1 tournament steps
-        kind = 1 if ostep == 0 else 2
+        inner_pair, nst = (bj_within_pair, B - 1) if ostep == 0 else (bj_cross_pair, B)
         for pi in range(nbc // 2):
-            g = gidx(bj_pair_sched(pi, ostep, nbc, True))
-            for st in range(B - 1 if kind == 1 else B):
-                pairs = [bj_inner_pair(i, st, kind) for i in range(B)]
+            g = gidx(bj_pair_sched(pi, ostep, nbc))
+            for st in range(nst):
+                pairs = [inner_pair(i, st) for i in range(B)]
                 assert sorted(itertools.chain.from_iterable(pairs)) == list(range(W))  # 32 disjoint pairs per inner step
                 for p, q in pairs:
                     key = (int(g[p]), int(g[q]))
@@ -72,12 +72,14 @@ def test_every_pair_once_schedule_rotates_every_index_pair_exactly_once_per_swee
     assert len(seen) == K * (K - 1) // 2 and set(seen.values()) == {1}
 
 
-def _inner(S, g, k, thr, kind):
+def _inner(S, g, k, thr, within):
+    """one inner sweep of a 64 x 64 subproblem: the within sweep (outer step 0) or the cross sweep"""
     S, Q, offmax, rotated = S.copy(), np.eye(W), 0.0, False
-    for st in range({0: W - 1, 1: B - 1, 2: B}[kind]):
+    inner_pair, nst = (bj_within_pair, B - 1) if within else (bj_cross_pair, B)
+    for st in range(nst):
         J, rot = np.eye(W), []
         for i in range(B):
-            p, q = bj_inner_pair(i, st, kind)
+            p, q = inner_pair(i, st)
             apq = S[p, q]
             if g[q] < k:
                 offmax = max(offmax, abs(apq))
@@ -99,7 +101,7 @@ def _inner(S, g, k, thr, kind):
     return Q, S, rotated, offmax
 
 
-def _project(Ain, k, cross, scan=False):
+def _project(Ain, k, scan=False):
     K64 = (k + W - 1) // W * W
     nbc, npairs = K64 // B, K64 // W
     A = [np.zeros((K64, K64)), np.zeros((K64, K64))]
@@ -107,11 +109,10 @@ def _project(Ain, k, cross, scan=False):
     V, cur, thr = np.eye(K64), 0, 1e-15 * np.linalg.norm(Ain) / k
     for sweep in range(1, 31):
         off = 0.0
-        for ostep in range(nbc if cross else nbc - 1):
-            kind = 0 if not cross else (1 if ostep == 0 else 2)
+        for ostep in range(nbc):
             old, new = A[cur], A[cur ^ 1]
-            pairs = [gidx(bj_pair_sched(pi, ostep, nbc, cross)) for pi in range(npairs)]
-            res = [_inner(old[np.ix_(g, g)], g, k, thr, kind) for g in pairs]
+            pairs = [gidx(bj_pair_sched(pi, ostep, nbc)) for pi in range(npairs)]
+            res = [_inner(old[np.ix_(g, g)], g, k, thr, ostep == 0) for g in pairs]
             off = max([off] + [r[3] for r in res])
             for P in range(npairs):
                 for Qp in range(npairs):
@@ -130,19 +131,19 @@ def _project(Ain, k, cross, scan=False):
             cur ^= 1
         if off <= thr:
             return A[cur], V, sweep
-        if scan:  # round 6 (psd_big.h, k_bp_offscan / the last update's left_bits): would the NEXT sweep rotate anything?
+        if scan:  # round 6 (psd_big.h, the last update's left_bits): would the NEXT sweep rotate anything?
             left = np.abs(A[cur][:k, :k] - np.diag(np.diag(A[cur][:k, :k]))).max()
             if left <= thr:
                 return A[cur], V, sweep
     return A[cur], V, 31
 
 
-@pytest.mark.parametrize("k,cross", [(100, True), (100, False), (131, True)])
-def test_emulated_blocked_iteration_converges_to_the_eigen_decomposition(k, cross):
+@pytest.mark.parametrize("k", [100, 131])
+def test_emulated_blocked_iteration_converges_to_the_eigen_decomposition(k):
     rng = np.random.default_rng(k)
     M = rng.standard_normal((k, k))
     Ain = (M + M.T) / 2
-    D, V, sweeps = _project(Ain, k, cross)
+    D, V, sweeps = _project(Ain, k)
     lam, Vk = np.diag(D)[:k], V[:k, :k]
     assert sweeps <= 13
     assert np.abs((Vk * lam) @ Vk.T - Ain).max() <= 1e-11
@@ -190,8 +191,8 @@ def _fused_subproblem(old, pairs_k, res_k, g_next):
     return S
 
 
-@pytest.mark.parametrize("k,cross", [(200, True), (131, False)])
-def test_fused_step_forms_the_subproblem_the_update_writes(k, cross):
+@pytest.mark.parametrize("k", [200])
+def test_fused_step_forms_the_subproblem_the_update_writes(k):
     """The index bookkeeping of k_bj_fused (psd_big.h): for every outer step of two sweeps, the subproblem assembled from pre-update
     data equals the diagonal block of the updated matrix for the next step's pairing."""
     rng = np.random.default_rng(k)
@@ -202,14 +203,13 @@ def test_fused_step_forms_the_subproblem_the_update_writes(k, cross):
     A = [np.zeros((K64, K64)), np.zeros((K64, K64))]
     A[0][:k, :k] = Ain
     cur, thr = 0, 1e-15 * np.linalg.norm(Ain) / k
-    osteps = nbc if cross else nbc - 1
+    osteps = nbc
     checked = 0
     for sweep in range(2):
         for ostep in range(osteps):
-            kind = 0 if not cross else (1 if ostep == 0 else 2)
             old, new = A[cur], A[cur ^ 1]
-            pairs = [gidx(bj_pair_sched(pi, ostep, nbc, cross)) for pi in range(npairs)]
-            res = [_inner(old[np.ix_(g, g)], g, k, thr, kind) for g in pairs]
+            pairs = [gidx(bj_pair_sched(pi, ostep, nbc)) for pi in range(npairs)]
+            res = [_inner(old[np.ix_(g, g)], g, k, thr, ostep == 0) for g in pairs]
             for P in range(npairs):
                 for Qp in range(npairs):
                     gp, gq, fP, fQ = pairs[P], pairs[Qp], res[P][2], res[Qp][2]
@@ -223,7 +223,7 @@ def test_fused_step_forms_the_subproblem_the_update_writes(k, cross):
                         new[np.ix_(gp, gq)] = QP.T @ (old[np.ix_(gp, gq)] @ QQ)
             nstep = (ostep + 1) % osteps  # the last launch of a sweep runs the first inner sweep of the next one
             for pi in range(npairs):
-                g_next = gidx(bj_pair_sched(pi, nstep, nbc, cross))
+                g_next = gidx(bj_pair_sched(pi, nstep, nbc))
                 got = _fused_subproblem(old, pairs, res, g_next)
                 want = new[np.ix_(g_next, g_next)]
                 assert np.abs(got - want).max() <= 1e-13 * max(1.0, np.abs(want).max()), (sweep, ostep, pi)
@@ -286,16 +286,16 @@ def test_incremental_round_robin_positions_equal_the_closed_form(K2):
     assert len(met) == K2 * (K2 - 1) // 2
 
 
-@pytest.mark.parametrize("k,cross", [(100, True), (70, False)])
-def test_closing_by_a_scan_ends_one_sweep_earlier_with_the_same_matrix(k, cross):
+@pytest.mark.parametrize("k", [100])
+def test_closing_by_a_scan_ends_one_sweep_earlier_with_the_same_matrix(k):
     """Round 6: the iteration used to end with a sweep that meets no entry above the threshold, i.e. one that rotates nothing.  Reading
-    the largest off-diagonal entry off the matrix after every sweep (psd_big.h: k_bp_offscan, or the last update of the sweep itself)
+    the largest off-diagonal entry off the matrix after every sweep (psd_big.h: the last update of the sweep records it, left_bits)
     ends it exactly one sweep earlier and leaves A and V bit for bit as the closing sweep would have (that sweep changes nothing)."""
     rng = np.random.default_rng(7 * k)
     M = rng.standard_normal((k, k))
     Ain = (M + M.T) / 2
-    D0, V0, s0 = _project(Ain, k, cross)
-    D1, V1, s1 = _project(Ain, k, cross, scan=True)
+    D0, V0, s0 = _project(Ain, k)
+    D1, V1, s1 = _project(Ain, k, scan=True)
     assert s1 == s0 - 1
     assert np.array_equal(D0, D1) and np.array_equal(V0, V1)
 
