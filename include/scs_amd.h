@@ -195,6 +195,25 @@ typedef struct {
 ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
 /* replaces src/scs.c:1287 */
 scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c);
+/* Extension (not in the reference; OSQP / Clarabel users know it as update_A / update_P): NEW VALUES of A and / or P on the pattern
+ * given to scs_init -- scs_init's value-dependent half again, without its pattern-dependent half (the numbering of reorder.h, the
+ * pattern transposes, the row units of the wave layouts, every kernel choice: all of them read the pattern only and stay as taken).
+ * Ax, Px: host arrays in the CALLER's order, the CSC arrays of d->A / d->P as given to scs_init (P: upper triangle); either may be
+ * NULL (that matrix keeps its values); both NULL is a no-op returning 0.
+ * After a successful call the workspace is in the state scs_init would have produced on the same pattern, cones and settings with the
+ * new values and the b, c most recently set (scs_init or scs_update): a solve returns the bits a fresh workspace returns.  In detail:
+ * the renumbering decided at init is kept and the values follow the entry permutation recorded with it (host, nnz entry positions,
+ * only when the renumbering is active); the equilibration runs again from the new raw values, through the passes scs_init took (host
+ * or device: bit-identical); D, E, primal_scale, dual_scale are replaced and b, c normalised again from the originals; every value copy
+ * of the linear system, the layouts and the preconditioner follow (scs_amd_linsys_update_values); stgs.scale goes back to the value
+ * given to scs_init -- an adapted scale does not carry over -- and diag_r with it; the box cone's normalised bounds are rebuilt and the
+ * warm starts of the box and PSD projections (single and block) are cold again; both Anderson memories start empty, as before every
+ * solve.  The family state of scs_amd_solve_family caches nothing that depends on the values.  With P the workspace also keeps the
+ * raw values of both matrices on the host (the one an update does not name is equilibrated again from them).
+ * -1 before any device call, the workspace untouched: w NULL, Px on a workspace without P, a non-finite value.  -1 on a HIP failure
+ * (message on stderr): the workspace is then STALE -- scs_solve and scs_amd_solve_family return SCS_FAILED, NaN-filled, until an
+ * update succeeds.  info.setup_time of the next solve is this call's time, as after scs_update.  Returns with the stream idle. */
+scs_int scs_amd_update_matrix(ScsWork *w, const scs_float *Ax, const scs_float *Px);
 /* replaces src/scs.c:1327 -- the device-resident ADMM loop */
 scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info,
                   scs_int warm_start);
@@ -218,6 +237,21 @@ scs_int scs_solve_lin_sys(ScsLinSysWork *w, scs_float *b, const scs_float *s,
 /* replaces private.c:327 (caller src/scs.c:1220) */
 scs_int scs_update_lin_sys_diag_r(ScsLinSysWork *w,
                                   const scs_float *new_diag_r);
+/* Extension: new values for the matrices of a live workspace, in the CSC order of the A (and P, upper triangle) handed to
+ * scs_init_lin_sys_work; the pattern is the one given then.  Ax or Px may be NULL (that matrix keeps its values).
+ * Afterwards the workspace cannot be told from one scs_init_lin_sys_work created on the new values: CSC(A) as given, CSR(A), the value
+ * arrays of the wave-owned-rows layouts (plain, lockstep, wide: whichever was built), the symmetric P and its diagonal sums, the Jacobi
+ * preconditioner under the diag_r in force; every decision taken at init (kernel choice, captured graphs, pacing) stays as taken, and
+ * the block entries and small-system paths read the same arrays.  The values are uploaded once and gathered on the device through
+ * position maps that the FIRST update builds and the workspace frees: nnz(A) entry positions (CSR position -> CSC position, formed on the
+ * device from the two patterns in HBM), and with P nnz(full P) entry positions + nnz(upper P) values of staging (the map of P is replayed
+ * once on the host from the symmetric copy, which requires the P given at init to have been an upper triangle).  Entry positions are
+ * 4 bytes, 8 in the DLONG build.  The layouts store no map: the builder that made a layout runs again on the refreshed CSR copy -- the
+ * device builder, or the HOST builder (one download and one pass) for a layout it made (a unit beyond 8192 entries, wr_build=host) --
+ * so their bytes equal a fresh build's.  No other host pass over the entries than the finiteness check.
+ * 0 on success; -1 on bad arguments (w NULL, a row-sharded workspace, Px given for a workspace without P, a non-finite value --
+ * checked before any device call, the workspace untouched) or on a HIP failure (message on stderr).  Returns with the stream idle. */
+scs_int scs_amd_linsys_update_values(ScsLinSysWork *w, const scs_float *Ax, const scs_float *Px);
 /* replaces private.c:333 (caller src/scs.c:1493) */
 void scs_free_lin_sys_work(ScsLinSysWork *w);
 /* replaces private.c:221 (callers src/scs.c:127,1346) */
@@ -422,6 +456,12 @@ scs_int scs_amd_get_spmv_kernel_name(const ScsWork *w, scs_int which, char *buf,
  * col_new2old (n) and row_new2old (m) receive new index -> caller's index (identity when nothing is kept); info (6 doubles, may be
  * NULL) as scs_amd_get_reorder_info.  Returns 1 if a renumbering is kept, 0 if not, < 0 on error. */
 scs_int scs_amd_plan_reorder(const ScsMatrix *A, const ScsCone *k, scs_int *col_new2old, scs_int *row_new2old, double *info);
+/* The same plus the ENTRY permutation scs_amd_update_matrix follows: entry o of the renumbered matrix A[row_new2old][:, col_new2old]
+ * (row indices sorted inside every column) is entry entry_new2old[o] (nnz of them) of A's arrays; the identity when nothing is kept.
+ * info (7 doubles, may be NULL): the six above, then 1 if the renumbered matrix was built beside the measurement of the candidate,
+ * 0 if afterwards -- the two ways scs_init comes by it; both record the same permutation. */
+scs_int scs_amd_plan_reorder_entries(const ScsMatrix *A, const ScsCone *k, scs_int *col_new2old, scs_int *row_new2old,
+                                     scs_int *entry_new2old, double *info);
 /* measurement hook: recompute the residuals after every ADMM iteration, where the reference does when
  * `log_csv_filename` is set (src/scs.c:1449-1454).  Those norms feed the next iteration's CG tolerance
  * (src/scs.c:745-762): a logged reference run follows a tighter schedule than an unlogged one, and this puts

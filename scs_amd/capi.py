@@ -129,6 +129,9 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
         lib.scs_free_lin_sys_work.argtypes = [C.c_void_p]
         lib.scs_get_lin_sys_method.restype = C.c_char_p
         lib.scs_get_lin_sys_method.argtypes = []
+        if stats:  # extension of the HIP libraries (the `linsys` branch alone also binds the reference backend)
+            lib.scs_amd_linsys_update_values.restype = scs_int
+            lib.scs_amd_linsys_update_values.argtypes = [C.c_void_p, fp, fp]
     if cones:
         lib.scs_amd_cone_init.restype = C.c_void_p
         lib.scs_amd_cone_init.argtypes = [C.POINTER(T.ScsCone), scs_int, fp]
@@ -251,6 +254,10 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_shard_set_profiling.argtypes = [C.c_void_p, scs_int]
             lib.scs_amd_shard_free.restype = None
             lib.scs_amd_shard_free.argtypes = [C.c_void_p]
+            lib.scs_amd_update_matrix.restype = scs_int
+            lib.scs_amd_update_matrix.argtypes = [C.c_void_p, fp, fp]
+            lib.scs_amd_plan_reorder_entries.restype = scs_int
+            lib.scs_amd_plan_reorder_entries.argtypes = [C.POINTER(T.ScsMatrix), C.POINTER(T.ScsCone), T.ip, T.ip, T.ip, C.POINTER(C.c_double)]
             lib.scs_amd_plan_reorder.restype = scs_int
             lib.scs_amd_plan_reorder.argtypes = [C.POINTER(T.ScsMatrix), C.POINTER(T.ScsCone), T.ip, T.ip, C.POINTER(C.c_double)]
             lib.scs_amd_get_reorder_info.restype = None
@@ -350,6 +357,31 @@ class Problem:
     def sparse(self):
         import scipy.sparse as sp
         return sp.csc_matrix((self.Ax, self.Ai, self.Ap), shape=(self.m, self.n))
+
+    def values_of(self, M, which="A"):
+        """New values for A (or, which="P", for P) on the pattern this problem was built with, as the contiguous array the
+        update entries take (scs_amd_update_matrix, scs_amd_linsys_update_values).  M: a scipy sparse matrix -- canonicalised as the
+        constructor does (CSC, P's upper triangle, sorted indices) and required to have exactly the stored pattern -- or a 1-D array of
+        values in that CSC order.  ValueError on any mismatch; the library is not called."""
+        import scipy.sparse as sp
+        if which == "P" and self.matP is None:
+            raise ValueError("this problem has no P")
+        ind, ptr = (self.Ai, self.Ap) if which == "A" else (self.Pi, self.Pp)
+        shape = (self.m, self.n) if which == "A" else (self.n, self.n)
+        if sp.issparse(M):
+            if M.shape != shape:
+                raise ValueError(f"{which} has shape {M.shape}, the workspace was built for {shape}")
+            M = sp.csc_matrix(sp.triu(M)) if which == "P" else sp.csc_matrix(M)
+            M.sort_indices()
+            if len(M.indices) != len(ind) or not np.array_equal(M.indptr, ptr) or not np.array_equal(M.indices, ind):
+                raise ValueError(f"the sparsity pattern of {which} differs from the one the workspace was built with "
+                                 "(new values only; a new pattern needs a new workspace)")
+            vals = M.data
+        else:
+            vals = np.asarray(M)
+            if vals.ndim != 1 or vals.shape[0] != len(ind):
+                raise ValueError(f"{which} values must be a 1-D array of the {len(ind)} stored entries in CSC order")
+        return np.ascontiguousarray(vals, dtype=self.T.np_float)
 
 
 def make_cone(cone, T=T64, keep=None):

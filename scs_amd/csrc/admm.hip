@@ -396,6 +396,12 @@ struct SCS_WORK {
   bool profiling = false;
   long long cone_projs = 0;
   FamilyWork *fam = nullptr;
+  // scs_amd_update_matrix: what an update needs beyond the above
+  real scale0 = 0;               // stgs.scale as given to scs_init (an adaptive-scale solve moves stgs.scale; an update puts it back)
+  bool dev_eq = false;           // where scs_init equilibrated: an update takes the same passes
+  std::vector<real> A_raw, P_raw; // un-equilibrated values in the internal order; only with P and normalize (the matrix an update does not
+                                 // name is equilibrated again from them; without P there is only A, and an update names it)
+  bool stale = false;            // an update failed half way: no solve until one succeeds
   ~SCS_WORK() {
     family_free(fam);
     if (log_csv_fout) fclose(log_csv_fout);
@@ -1089,6 +1095,66 @@ scs_int scs_update(ScsWork *w, scs_float *b, scs_float *c) { // src/scs.c:1287-1
   return 0;
 }
 
+// scs_init's value-dependent half again (include/scs_amd.h).  The numbering, the pattern transposes, the row units of the layouts and
+// every kernel choice are the pattern's and stay; what follows the values is redone in scs_init's order: renumbered values (the entry
+// permutation recorded with the renumbering), equilibration (the passes scs_init took), D / E / the scales, b and c normalised again, every
+// value copy of the linear system (LinSys::update_values: gathers on the device), the scale and diag_r of scs_init, the preconditioner,
+// the cone's D-dependent state and warm starts.
+scs_int scs_amd_update_matrix(ScsWork *w, const scs_float *Ax, const scs_float *Px) {
+  if (!w || (Px && !w->has_P)) return -1;
+  const size_t nzA = w->A.x.size(), nzP = w->has_P ? w->P.x.size() : 0;
+  if ((Ax && !all_finite(Ax, nzA)) || (Px && !all_finite(Px, nzP))) return -1;
+  if (!Ax && !Px) return 0;
+  const double t0 = now_ms();
+  const bool dbg = opt_get("debug") != nullptr;
+  double tp = t0;
+  auto phase = [&](const char *what) {
+    if (dbg) fprintf(stderr, "[scs_amd update] %-22s %8.1f ms\n", what, now_ms() - tp);
+    tp = now_ms();
+  };
+  try {
+    w->stale = true; // until the last step below has run
+    HIP_CHECK(hipSetDevice(w->device));
+    const bool norm = w->stgs.normalize != 0;
+    if (norm && w->has_P) { // both matrices are equilibrated together: the one not named starts from its raw values again
+      if (Ax) std::copy(Ax, Ax + nzA, w->A_raw.begin()); // (P switches the renumbering off: the caller's order is the internal one)
+      if (Px) std::copy(Px, Px + nzP, w->P_raw.begin());
+      w->A.x = w->A_raw;
+      w->P.x = w->P_raw;
+    } else {
+      if (Ax) permute_values(w->reord, Ax, nzA, w->A.x.data());
+      if (Px) std::copy(Px, Px + nzP, w->P.x.begin());
+    }
+    phase("values");
+    if (norm) {
+      if (w->dev_eq) equilibrate_dev(w->has_P ? &w->P : nullptr, w->A, &w->k, w->scal, w->stream, nullptr);
+      else equilibrate(w->has_P ? &w->P : nullptr, w->A, &w->k, w->scal);
+      w->D.upload(w->scal.D.data(), w->m, w->stream);
+      w->E.upload(w->scal.E.data(), w->n, w->stream);
+      HIP_CHECK(hipStreamSynchronize(w->stream));
+    }
+    phase("equilibrate");
+    if (scs_update(w, nullptr, nullptr) != 0) throw HipError("scs_amd: scs_update failed"); // b_orig, c_orig under the new D, E and scales
+    phase("b, c");
+    w->ls.update_values((norm || Ax) ? w->A.x.data() : nullptr, w->has_P && (norm || Px) ? w->P.x.data() : nullptr);
+    phase("linsys values");
+    w->stgs.scale = w->scale0;
+    set_diag_r(w);
+    w->ls.set_diag_r_dev(w->diag_r.p);
+    w->cone.update_scaling(&w->k, norm ? w->scal.D.data() : nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(w->stream));
+    phase("scale, cones");
+    w->stale = false;
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(w->stream);
+    return -1;
+  }
+  w->setup_time = now_ms() - t0;
+  return 0;
+}
+
 ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) { // :1245-1285, :982-1116
   if (!d || !k || !stgs) {
     printf("ERROR: Missing ScsData, ScsCone, or ScsSettings input\n");
@@ -1109,6 +1175,7 @@ ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
     w->device = dev;
     const int n = w->n = d->n, m = w->m = d->m, l = w->l = d->n + d->m + 1;
     w->stgs = *stgs;
+    w->scale0 = stgs->scale;
     if (stgs->write_data_filename) { // src/scs.c:1272-1275
       printf("Writing raw problem data to %s\n", stgs->write_data_filename);
       write_problem(d, k, stgs, stgs->write_data_filename);
@@ -1158,6 +1225,11 @@ ScsWork *scs_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs) {
       // the ~200 launches to be cheaper than the host loops (SCS_AMD_EQUIL=host|dev forces)
       bool dev_eq = (long long)d->A->p[n] >= 100000;
       if (const char *e = opt_get("equil")) dev_eq = strcmp(e, "host") != 0;
+      w->dev_eq = dev_eq;
+      if (w->has_P) { // (see SCS_WORK::A_raw)
+        w->A_raw = w->A.x;
+        w->P_raw = w->P.x;
+      }
       if (dev_eq) equilibrate_dev(w->has_P ? &w->P : nullptr, w->A, &w->k, w->scal, w->stream, &a_pattern);
       else equilibrate(w->has_P ? &w->P : nullptr, w->A, &w->k, w->scal);
     } else {
@@ -1451,6 +1523,7 @@ scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_star
     printf("ERROR: missing ScsWork, ScsSolution or ScsInfo input\n");
     return SCS_FAILED;
   }
+  if (w->stale) return fail_out(w, w->m, w->n, sol, info, SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
   InterruptListener listener; // :1344, restored on every return below (:369, :1482)
   try {
     solve_begin(w, sol, warm_start);
@@ -1474,7 +1547,7 @@ scs_int scs_solve(ScsWork *w, ScsSolution *sol, ScsInfo *info, scs_int warm_star
 
 // ---- instrumentation: the same solve in three calls (not in the reference) ------
 scs_int scs_amd_solve_begin(ScsWork *w, const ScsSolution *sol, scs_int warm_start) {
-  if (!w) return -1;
+  if (!w || w->stale) return -1;
   try {
     solve_begin(w, sol, warm_start);
     HIP_CHECK(hipStreamSynchronize(w->stream));
@@ -1578,6 +1651,40 @@ scs_int scs_amd_plan_reorder(const ScsMatrix *A, const ScsCone *k, scs_int *col_
       info[3] = R.after[0];
       info[4] = R.after[1];
       info[5] = R.seconds;
+    }
+    return R.active ? 1 : 0;
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+}
+
+// scs_amd_plan_reorder plus the entry permutation that goes with the numbering: entry o of the renumbered matrix (row indices sorted inside
+// every column) is entry entry_new2old[o] of A's arrays; the identity when no renumbering is kept.  info (optional) holds 7 numbers: the
+// six of scs_amd_get_reorder_info, then 1 if the renumbered matrix was built beside the measurement of the candidate (0: by apply_reorder).
+scs_int scs_amd_plan_reorder_entries(const ScsMatrix *A, const ScsCone *k, scs_int *col_new2old, scs_int *row_new2old, scs_int *entry_new2old,
+                                     double *info) {
+  if (!A || !k || !col_new2old || !row_new2old || !entry_new2old) return -1;
+  if (k->z < 0 || k->l < 0 || (long long)k->z + k->l > (long long)A->m) return -1;
+  try {
+    HostCsc a;
+    a.copy_from(A);
+    Reorder R;
+    plan_reorder(a, k, false, R);
+    const bool ready = R.active && R.have_ready;
+    if (R.active) apply_reorder(a, R);
+    for (scs_int j = 0; j < A->n; ++j) col_new2old[j] = R.active ? (scs_int)R.col_new2old[j] : j;
+    for (scs_int i = 0; i < A->m; ++i) row_new2old[i] = R.active ? (scs_int)R.row_new2old[i] : i;
+    const size_t nnz = a.x.size();
+    for (size_t o = 0; o < nnz; ++o) entry_new2old[o] = R.active ? (scs_int)R.entry_new2old[o] : (scs_int)o;
+    if (info) {
+      info[0] = R.active ? 1 : 0;
+      info[1] = R.before[0];
+      info[2] = R.before[1];
+      info[3] = R.after[0];
+      info[4] = R.after[1];
+      info[5] = R.seconds;
+      info[6] = ready ? 1 : 0;
     }
     return R.active ? 1 : 0;
   } catch (const std::exception &ex) {

@@ -655,6 +655,11 @@ scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob, const scs_float *B, scs_
     printf("ERROR: %s\n", why);
     return SCS_FAILED;
   }
+  if (w->stale) { // the last scs_amd_update_matrix failed half way
+    for (scs_int k = 0; k < nprob; ++k)
+      fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
+    return SCS_FAILED;
+  }
   InterruptListener listener;
   scs_int done = 0; // columns already returned
   try {

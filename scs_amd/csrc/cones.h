@@ -69,6 +69,8 @@ struct ConeDev {
   DevBuf<real> x_stage, s_stage, r_stage;
 
   void init(const ScsCone *k, int m, const real *D_host, hipStream_t s);
+  void upload_box_bounds(const ScsCone *k, const real *D_host); // bl / bu (allocated) from the cone's bounds and D
+  void update_scaling(const ScsCone *k, const real *D_host);    // a new D on the same cone: bounds again, every warm start as after init
   // cw (device, length m) <- Proj_K(cw), projection under the diag(r_y)^-1 metric
   // (only the box cone looks at r_y; nullptr = Euclidean).
   void proj_primal(real *cw, const real *r_y);

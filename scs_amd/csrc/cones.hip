@@ -976,6 +976,38 @@ static inline int small_grid(long long len) {
   return (int)std::max<long long>(1, std::min<long long>(g, 2048));
 }
 
+// normalize_box_cone (cones.c:1161-1177) applied to a private copy.  The reference only calls it when a
+// scaling exists (cones.c:1561: `if (scal)`), so without one the bounds are used exactly as given -- a
+// "1e20 = infinite" bound then stays the finite number 1e20, as in the reference
+void ConeDev::upload_box_bounds(const ScsCone *k, const real *D) {
+  std::vector<real> hl(bsize - 1), hu(bsize - 1);
+  const real *Db = D ? D + box_off : nullptr;
+  for (int j = 0; j < bsize - 1; ++j) {
+    if (!Db) {
+      hu[j] = k->bu[j];
+      hl[j] = k->bl[j];
+      continue;
+    }
+    const real f = Db[j + 1] / Db[0];
+    hu[j] = k->bu[j] >= (real)MAX_BOX_VAL ? (real)INFINITY : k->bu[j] * f;
+    hl[j] = k->bl[j] <= (real)-MAX_BOX_VAL ? (real)-INFINITY : k->bl[j] * f;
+  }
+  bl.upload(hl.data(), bsize - 1, stream);
+  bu.upload(hu.data(), bsize - 1, stream);
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// A new row scaling D on the same cone (scs_amd_update_matrix): what init derived from D -- the box cone's normalised bounds -- again,
+// and every warm start back to where init left it (box Newton start 1, cold eigenbases; the block state too when it exists)
+void ConeDev::update_scaling(const ScsCone *k, const real *D) {
+  if (bsize > 1) upload_box_bounds(k, D);
+  const real one = 1; // cones.c:1560
+  box_t.upload(&one, 1, stream);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  reset_warm_start();
+  if (multi) reset_multi_cold();
+}
+
 void ConeDev::init(const ScsCone *k, int m_, const real *D, hipStream_t s) {
   m = m_;
   stream = s;
@@ -985,26 +1017,9 @@ void ConeDev::init(const ScsCone *k, int m_, const real *D, hipStream_t s) {
   box_off = z + l;
   int off = z + l;
   if (bsize > 1) {
-    // normalize_box_cone (cones.c:1161-1177) applied to a private copy.  The reference only calls it when a
-    // scaling exists (cones.c:1561: `if (scal)`), so without one the bounds are used exactly as given -- a
-    // "1e20 = infinite" bound then stays the finite number 1e20, as in the reference
-    std::vector<real> hl(bsize - 1), hu(bsize - 1);
-    const real *Db = D ? D + box_off : nullptr;
-    for (int j = 0; j < bsize - 1; ++j) {
-      if (!Db) {
-        hu[j] = k->bu[j];
-        hl[j] = k->bl[j];
-        continue;
-      }
-      const real f = Db[j + 1] / Db[0];
-      hu[j] = k->bu[j] >= (real)MAX_BOX_VAL ? (real)INFINITY : k->bu[j] * f;
-      hl[j] = k->bl[j] <= (real)-MAX_BOX_VAL ? (real)-INFINITY : k->bl[j] * f;
-    }
     bl.alloc(bsize - 1);
     bu.alloc(bsize - 1);
-    bl.upload(hl.data(), bsize - 1, stream);
-    bu.upload(hu.data(), bsize - 1, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
+    upload_box_bounds(k, D);
   }
   box_t.alloc(1);
   box_multi = bsize - 1 >= BOX_MULTI_MIN;

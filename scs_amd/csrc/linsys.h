@@ -182,6 +182,19 @@ struct LinSys {
   void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr);
   void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
   void solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out);
+  // ---- new values on the pattern given to init (scs_amd_linsys_update_values, include/scs_amd.h) ----
+  // Position maps, device resident, built by the first update that needs them and freed with the workspace:
+  //   upd_rpos  nnz(A) x sizeof(eoff)            CSC position of every CSR(A) entry (the pattern transpose, formed on the device)
+  //   upd_fsrc  nnz(full P) x sizeof(eoff)       position in the upper triangle of every entry of the symmetric P
+  //   upd_pux   nnz(upper P) x sizeof(real)      where the caller's Px lands before the gather
+  // The wave layouts keep no map: the builder that made them runs again on the refreshed CSR copy (wave_refresh_values).
+  DevBuf<eoff> upd_rpos, upd_fsrc;
+  DevBuf<real> upd_pux;
+  long long nnzP_up = 0; // entries of the upper triangle handed to init
+  void ensure_update_maps(bool need_A, bool need_P);
+  // Ax / Px: HOST arrays in the CSC order of init's A / P (either may be null); every value copy, the layouts and the preconditioner
+  // follow; returns with the stream idle
+  void update_values(const real *Ax, const real *Px);
   long long matvec_bytes() const { return A.algorithmic_bytes() + At.algorithmic_bytes(); }
   void harvest_timers();
   void get_cg_pacing(long long out[4]) const; // scs_amd_get_cg_pacing (include/scs_amd.h)

@@ -1035,6 +1035,7 @@ void LinSys::init(const CscView *A_csc, const CscView *P_csc, hipStream_t s, Csr
     const eoff *Pp_ = P_csc->p;
     const int *Pi = P_csc->i;
     const real *Px = P_csc->x;
+    nnzP_up = Pp_[n];
     std::vector<eoff> cnt((size_t)n + 1, 0);
     std::vector<real> pd((size_t)n, 0);
     for (int j = 0; j < n; ++j)
@@ -1165,6 +1166,126 @@ void LinSys::build_preconditioner() {
     shard_allreduce(M.p, (size_t)n, 0);
     hipLaunchKernelGGL(k_reciprocal, dim3(vec_grid(n)), dim3(SCSAMD_BLOCK), 0, stream, M.p, n);
   }
+}
+
+// ----------------------------------------------------------------------------
+// New values on the pattern given to init (scs_amd_linsys_update_values): the values are uploaded once and gathered through
+// device-resident position maps into every copy; no host pass over the entries, no sort, no transpose on the host.
+// ----------------------------------------------------------------------------
+// CSC position of every CSR(A) entry, from the two patterns already in HBM: entry k of CSC(A) (= CSR(A'), `At`) lies in column j (binary
+// search in the column pointers) and row i; its CSR position is where j stands among the ascending columns of row i (binary search), plus
+// -- only when (i, j) is stored more than once -- the number of earlier entries of column j with the same row (rows of CSR(A) keep equal
+// columns in CSC order, as both transposes of init leave them).  Entry positions may carry the DLONG test bias; the map holds plain ones.
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_upd_map_rpos(CsrView At, CsrView A, long long nnz, eoff bias, eoff *__restrict__ rpos) {
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (long long)gridDim.x * blockDim.x) {
+    const eoff q = (eoff)k + bias;
+    int lo = 0, hi = At.rows; // At.ptr[lo] <= q < At.ptr[hi]
+    while (hi - lo > 1) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (At.ptr[mid] <= q) lo = mid;
+      else hi = mid;
+    }
+    const int j = lo, i = At.idx[q];
+    eoff a = A.ptr[i], z = A.ptr[i + 1];
+    const eoff zend = z;
+    while (a < z) { // first entry of row i whose column is >= j
+      const eoff mid = a + ((z - a) >> 1);
+      if (A.idx[mid] < j) a = mid + 1;
+      else z = mid;
+    }
+    if (a + 1 < zend && A.idx[a + 1] == j)
+      for (eoff q2 = At.ptr[j]; q2 < q; ++q2) a += At.idx[q2] == i ? 1 : 0;
+    if ((long long)(a - bias) < nnz) rpos[a - bias] = (eoff)k; // (always, for the orders init leaves; never past the map)
+  }
+}
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_upd_gather(const real *__restrict__ src, const eoff *__restrict__ map, real *__restrict__ dst,
+                                                             long long len) {
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < len; k += (long long)gridDim.x * blockDim.x) dst[k] = src[map[k]];
+}
+// Pdiag[j] = sum of the stored diagonal entries of column j in their CSC order (private.c:69-75): in row j of the symmetric P those are the
+// entries with column j, in the same order (init puts a column's own entries first)
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_upd_pdiag(CsrView P, real *__restrict__ pd) {
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < P.rows; j += gridDim.x * blockDim.x) {
+    real s = 0;
+    for (eoff k = P.ptr[j]; k < P.ptr[j + 1]; ++k)
+      if (P.idx[k] == j) s += P.val[k];
+    pd[j] = s;
+  }
+}
+
+static inline int upd_grid(long long len) { // streaming passes over the entries: enough workgroups to fill the chip, grid-strided beyond
+  return (int)std::max<long long>(1, std::min<long long>((len + SCSAMD_BLOCK - 1) / SCSAMD_BLOCK, 8192));
+}
+
+void LinSys::ensure_update_maps(bool need_A, bool need_P) {
+  if (need_A && !upd_rpos.p && At.nnz > 0) {
+    upd_rpos.alloc((size_t)At.nnz);
+    hipLaunchKernelGGL(k_upd_map_rpos, dim3(upd_grid(At.nnz)), dim3(SCSAMD_BLOCK), 0, stream, At.view(), A.view(), At.nnz, (eoff)At.bias,
+                       upd_rpos.p);
+    HIP_CHECK(hipGetLastError());
+  }
+  if (need_P && has_P && !upd_fsrc.p) {
+    // the symmetric P is the only copy of P's pattern the workspace holds: init put the entries of the upper column j first in row j
+    // (columns <= j), then the mirrors (row i < j of an entry (i, j): columns > i) in column order.  Replayed once, on the host, from the
+    // row pointers and columns of that copy -- the one pass over P's pattern an update ever makes.
+    const size_t nzf = (size_t)P.nnz;
+    std::vector<eoff> fp((size_t)n + 1);
+    std::vector<int> fj(nzf);
+    P.ptr.download(fp.data(), fp.size(), stream);
+    if (nzf) P.idx.download(fj.data(), nzf, stream);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (eoff &v : fp) v -= (eoff)P.bias;
+    std::vector<eoff> up((size_t)n + 1, 0), nxt((size_t)n), fsrc(nzf);
+    for (int r = 0; r < n; ++r) {
+      eoff own = 0;
+      while (fp[r] + own < fp[r + 1] && fj[(size_t)(fp[r] + own)] <= r) ++own;
+      up[(size_t)r + 1] = up[r] + own;
+      nxt[r] = fp[r] + own;
+    }
+    bool ok = (long long)up[n] == nnzP_up;
+    for (int j = 0; j < n && ok; ++j)
+      for (eoff t = fp[j]; t < fp[j] + (up[(size_t)j + 1] - up[j]); ++t) {
+        const eoff q = up[j] + (t - fp[j]);
+        const int i = fj[(size_t)t];
+        fsrc[(size_t)t] = q;
+        if (i != j) {
+          if (nxt[i] >= fp[(size_t)i + 1] || fj[(size_t)nxt[i]] != j) {
+            ok = false;
+            break;
+          }
+          fsrc[(size_t)nxt[i]++] = q;
+        }
+      }
+    if (!ok) throw HipError("scs_amd: the P handed to scs_init_lin_sys_work was not an upper triangle: its values cannot be updated in place");
+    upd_fsrc.alloc(nzf);
+    if (nzf) upd_fsrc.upload(fsrc.data(), nzf, stream);
+    upd_pux.alloc((size_t)nnzP_up);
+    HIP_CHECK(hipStreamSynchronize(stream)); // fsrc is a local
+  }
+}
+
+void LinSys::update_values(const real *Ax, const real *Px) {
+  if (shard) throw HipError("scs_amd: a row-sharded workspace takes no new matrix values");
+  if (Px && !has_P) throw HipError("scs_amd: new values of P for a workspace without P");
+  ensure_update_maps(Ax != nullptr, Px != nullptr);
+  if (Ax && At.nnz > 0) {
+    At.val.upload(Ax, (size_t)At.nnz, stream); // CSC(A) is CSR(A'): as given
+    hipLaunchKernelGGL(k_upd_gather, dim3(upd_grid(At.nnz)), dim3(SCSAMD_BLOCK), 0, stream, (const real *)At.val.p, (const eoff *)upd_rpos.p,
+                       A.val.p, At.nnz);
+    HIP_CHECK(hipGetLastError());
+    if (At.wave) wave_refresh_values(*At.wave, At, stream);
+    if (A.wave) wave_refresh_values(*A.wave, A, stream);
+  }
+  if (Px && P.nnz > 0) {
+    upd_pux.upload(Px, (size_t)nnzP_up, stream);
+    hipLaunchKernelGGL(k_upd_gather, dim3(upd_grid(P.nnz)), dim3(SCSAMD_BLOCK), 0, stream, (const real *)upd_pux.p, (const eoff *)upd_fsrc.p,
+                       P.val.p, P.nnz);
+    hipLaunchKernelGGL(k_upd_pdiag, dim3(vec_grid(n)), dim3(SCSAMD_BLOCK), 0, stream, P.view(), Pdiag.p);
+    HIP_CHECK(hipGetLastError());
+  }
+  build_preconditioner(); // with the diag_r in force
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream)); // the caller's arrays may be pageable and reused
 }
 
 void LinSys::set_shard(ShardHook *h) {
@@ -1774,6 +1895,28 @@ scs_int scs_update_lin_sys_diag_r(ScsLinSysWork *w, const scs_float *new_diag_r)
     HIP_CHECK(hipStreamSynchronize(w->ls.stream));
   } catch (const std::exception &ex) {
     fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
+}
+
+// every value finite?  (the one host pass over the entries an update makes)
+static bool all_finite(const scs_float *v, long long len) {
+  for (long long k = 0; k < len; ++k)
+    if (!std::isfinite((double)v[k])) return false;
+  return true;
+}
+
+scs_int scs_amd_linsys_update_values(ScsLinSysWork *w, const scs_float *Ax, const scs_float *Px) {
+  if (!w || w->ls.shard || (Px && !w->ls.has_P)) return -1;
+  if ((Ax && !all_finite(Ax, w->ls.At.nnz)) || (Px && !all_finite(Px, w->ls.nnzP_up))) return -1;
+  if (!Ax && !Px) return 0;
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    w->ls.update_values(Ax, Px);
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(w->ls.stream);
     return -1;
   }
   return 0;

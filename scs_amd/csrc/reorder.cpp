@@ -130,7 +130,8 @@ std::vector<int> order_by_key(const std::vector<double> &key) {
 
 } // namespace
 
-static void build_renumbered(const HostCsc &A, const std::vector<int> &col_new2old, const std::vector<int> &row_new2old, HostCsc &B);
+static void build_renumbered(const HostCsc &A, const std::vector<int> &col_new2old, const std::vector<int> &row_new2old, HostCsc &B,
+                             std::vector<eoff> &entry_new2old);
 
 double lines_per_entry(const eoff *ptr, const int *idx, int rows, int cols, size_t elem_bytes) {
   const long long nnz = ptr[rows];
@@ -472,9 +473,10 @@ void plan_reorder(const HostCsc &A, const ScsCone *k, bool has_P, Reorder &R) {
       // the renumbered matrix is built BESIDE the measurement (the candidate is kept on this family; a rejected one costs nothing but
       // the side threads' time): 0.43 -> 0.33 s of scs_init at n = 1e6
       HostCsc built;
+      std::vector<eoff> built_entry;
       {
         SideTask tbuild; // (joined before `built` is used or goes away)
-        tbuild.start([&] { build_renumbered(A, c3.col_new2old, c3.row_new2old, built); });
+        tbuild.start([&] { build_renumbered(A, c3.col_new2old, c3.row_new2old, built, built_entry); });
         measure(A, c3);
         tbuild.join();
       }
@@ -489,6 +491,7 @@ void plan_reorder(const HostCsc &A, const ScsCone *k, bool has_P, Reorder &R) {
         R.col_new2old = std::move(c3.col_new2old);
         R.row_new2old = std::move(c3.row_new2old);
         R.ready = std::move(built);
+        R.entry_new2old = std::move(built_entry);
         R.have_ready = true;
         R.why = "no hidden locality (anchored entries spread over the whole cone range); chain + home numbering shares 15 % or more of the gathers' lines";
       } else {
@@ -702,8 +705,10 @@ void plan_reorder(const HostCsc &A, const ScsCone *k, bool has_P, Reorder &R) {
             R.before[1], R.after[1], R.active ? "kept" : "dropped", 1e3 * R.seconds);
 }
 
-// B <- A[row_new2old, col_new2old], row indices sorted inside every column
-static void build_renumbered(const HostCsc &A, const std::vector<int> &col_new2old, const std::vector<int> &row_new2old, HostCsc &B) {
+// B <- A[row_new2old, col_new2old], row indices sorted inside every column; entry_new2old[o] = the position in A's arrays of entry o of B
+// (the entry permutation an update of the values repeats: scs_amd_update_matrix)
+static void build_renumbered(const HostCsc &A, const std::vector<int> &col_new2old, const std::vector<int> &row_new2old, HostCsc &B,
+                             std::vector<eoff> &entry_new2old) {
   const int m = A.m, n = A.n;
   std::vector<int> row_old2new((size_t)m);
   for (int i = 0; i < m; ++i) row_old2new[row_new2old[i]] = i;
@@ -712,19 +717,21 @@ static void build_renumbered(const HostCsc &A, const std::vector<int> &col_new2o
   B.p.assign((size_t)n + 1, 0);
   B.i.resize(A.i.size());
   B.x.resize(A.x.size());
+  entry_new2old.resize(A.x.size());
   for (int j = 0; j < n; ++j) B.p[j + 1] = B.p[j] + (A.p[col_new2old[j] + 1] - A.p[col_new2old[j]]);
   // columns are independent once B.p is known: ranges of them on a few host threads
   auto do_range = [&](int j0, int j1) {
-    std::vector<std::pair<int, real>> col;
+    std::vector<std::pair<int, eoff>> col; // (new row, position in A)
     for (int j = j0; j < j1; ++j) {
       const int jo = col_new2old[j];
       col.clear();
-      for (eoff q = A.p[jo]; q < A.p[jo + 1]; ++q) col.emplace_back(row_old2new[A.i[q]], A.x[q]);
-      std::stable_sort(col.begin(), col.end(), [](const std::pair<int, real> &a, const std::pair<int, real> &b) { return a.first < b.first; });
+      for (eoff q = A.p[jo]; q < A.p[jo + 1]; ++q) col.emplace_back(row_old2new[A.i[q]], q);
+      std::stable_sort(col.begin(), col.end(), [](const std::pair<int, eoff> &a, const std::pair<int, eoff> &b) { return a.first < b.first; });
       eoff o = B.p[j];
       for (const auto &e : col) {
         B.i[(size_t)o] = e.first;
-        B.x[(size_t)o] = e.second;
+        B.x[(size_t)o] = A.x[(size_t)e.second];
+        entry_new2old[(size_t)o] = e.second;
         ++o;
       }
     }
@@ -747,8 +754,23 @@ void apply_reorder(HostCsc &A, const Reorder &R) {
     return;
   }
   HostCsc B;
-  build_renumbered(A, R.col_new2old, R.row_new2old, B);
+  build_renumbered(A, R.col_new2old, R.row_new2old, B, R.entry_new2old);
   A = std::move(B);
+}
+
+bool all_finite(const real *v, size_t len) {
+  for (size_t k = 0; k < len; ++k)
+    if (!std::isfinite((double)v[k])) return false;
+  return true;
+}
+
+void permute_values(const Reorder &R, const real *src, size_t len, real *dst) {
+  if (!R.active) {
+    if (len) std::copy(src, src + len, dst);
+    return;
+  }
+  if (R.entry_new2old.size() != len) throw std::runtime_error("scs_amd: the entry permutation does not match the number of values");
+  for (size_t o = 0; o < len; ++o) dst[o] = src[(size_t)R.entry_new2old[o]];
 }
 
 } // namespace scsamd

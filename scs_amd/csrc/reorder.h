@@ -44,12 +44,20 @@ struct Reorder {
   // apply_reorder then only moves it into place
   mutable HostCsc ready;
   mutable bool have_ready = false;
+  // entry o of the renumbered matrix is entry entry_new2old[o] of the caller's arrays: nnz x sizeof(eoff) bytes on the host, recorded by
+  // whichever of the two ways builds the renumbered matrix (both run build_renumbered), only when the renumbering is active; new values
+  // on the same pattern follow it (scs_amd_update_matrix) instead of a second plan_reorder
+  mutable std::vector<eoff> entry_new2old;
 };
 
 // decides (and fills R); A is the caller's matrix (m x n CSC), k the cone
 void plan_reorder(const HostCsc &A, const ScsCone *k, bool has_P, Reorder &R);
 // A <- A[row_new2old, col_new2old], row indices sorted inside every column
 void apply_reorder(HostCsc &A, const Reorder &R);
+// the host half of a value update (scs_amd_update_matrix): is every value finite, and dst[o] = src[entry_new2old[o]] -- the caller's
+// CSC order into the internal one (a plain copy when the renumbering is not active); len = 0 touches neither array
+bool all_finite(const real *v, size_t len);
+void permute_values(const Reorder &R, const real *src, size_t len, real *dst);
 // distinct 128-byte lines of the gathered vector per entry, over units of consecutive rows of ~ nnz / 2048 entries
 double lines_per_entry(const eoff *ptr, const int *idx, int rows, int cols, size_t elem_bytes);
 

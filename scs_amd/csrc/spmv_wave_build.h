@@ -244,6 +244,52 @@ inline void wave_build(WaveRowsDev &w, int rows, int cols, const eoff *hptr, con
   }
   w.finish(distinct);
 }
+// New VALUES into a built layout whose pattern is unchanged (LinSys::update_values): `mat` already holds the new values in CSR order.
+// The builder that made the layout runs again on them -- k_wave_layout for a device-built layout (same keys, same sorts: wrd is rewritten
+// with the bytes it holds, val with the new values in the same slots), fill_host for a layout the HOST builder made (a unit beyond
+// WR_DEV_UNIT_MAX entries, SCS_AMD_WR_BUILD=host) -- so the bytes equal a fresh build's and no slot map is stored.  Entry positions may
+// carry the DLONG test bias (CsrDev::bias): the arrays go to the kernel shifted, as the product kernels get them.
+inline void wave_refresh_values(WaveRowsDev &w, const CsrDev &mat, hipStream_t st) {
+  if (!w.built) return;
+  if (w.built_on_device) {
+    const int lshift = sizeof(real) == 8 ? 4 : 5;
+    const long long lines = ((long long)w.cols >> lshift) + 1;
+    const int bm_words = WaveRowsDev::lines_counted(w.cols) ? (int)((lines + 31) / 32) : 0;
+    const size_t lds = WB_LDS_KEYS + WB_LDS_ROWL + (size_t)bm_words * 4; // what wave_fill_dev accepted when the layout was built
+    const void *kp = w.sub_window_order ? reinterpret_cast<const void *>(k_wave_layout<true>) : reinterpret_cast<const void *>(k_wave_layout<false>);
+    HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DevBuf<unsigned long long> cnt(1); // the distinct-line count is a property of the pattern: recounted, not used
+    const long long mb = mat.bias, wb = w.bias;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(w.nunit), dim3(WB_THREADS), lds, st, (const eoff *)mat.ptr.p, (const int *)(mat.idx.p - mb),
+                         (const real *)(mat.val.p - mb), (const int *)w.urow.p, (const eoff *)w.useg.p, w.wrd.p - wb, w.val.p - wb, w.cbits,
+                         w.bshift, lshift, bm_words, cnt.p, w.wide ? w.rowl.p - wb : (unsigned short *)nullptr);
+    };
+    if (w.sub_window_order) launch(k_wave_layout<true>);
+    else launch(k_wave_layout<false>);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st)); // cnt is a local
+    return;
+  }
+  const size_t nz = (size_t)mat.nnz;
+  std::vector<eoff> hp((size_t)mat.rows + 1);
+  std::vector<int> hi(nz);
+  std::vector<real> hx(nz);
+  mat.ptr.download(hp.data(), hp.size(), st);
+  if (nz) {
+    mat.idx.download(hi.data(), nz, st);
+    mat.val.download(hx.data(), nz, st);
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  for (eoff &p : hp) p -= (eoff)mat.bias;
+  std::vector<unsigned> hw;
+  std::vector<real> hv;
+  std::vector<unsigned short> hr;
+  long long dh = 0;
+  w.fill_host(hp.data(), hi.data(), hx.data(), hw, hv, dh, &hr);
+  w.val.upload(hv.data(), w.cap, st);
+  HIP_CHECK(hipStreamSynchronize(st)); // (wrd and rowl hold the pattern: unchanged)
+}
 #endif // __HIPCC__
 
 } // namespace scsamd

@@ -106,6 +106,20 @@ class LinSys:
         if self._lib.scs_update_lin_sys_diag_r(w, d.ctypes.data_as(T.fp)) != 0:
             raise RuntimeError("scs_update_lin_sys_diag_r failed")
 
+    def update_values(self, A_values=None, P_values=None):
+        """scs_amd_linsys_update_values: new values of A and / or P on the pattern given at construction (a scipy sparse matrix with
+        that pattern, or the values in its CSC order; P: upper triangle).  diag_r stays; single and block solves alike see the new
+        matrices.  ValueError for a different pattern or a non-finite value, before the library is called."""
+        w, T = self._work(), self._T
+        ax = None if A_values is None else self._prob.values_of(A_values, "A")
+        px = None if P_values is None else self._prob.values_of(P_values, "P")
+        for v in (ax, px):
+            if v is not None and not np.all(np.isfinite(v)):
+                raise ValueError("matrix values must be finite")
+        if self._lib.scs_amd_linsys_update_values(w, ax.ctypes.data_as(T.fp) if ax is not None else None,
+                                                  px.ctypes.data_as(T.fp) if px is not None else None) != 0:
+            raise RuntimeError("scs_amd_linsys_update_values failed")
+
     def stats(self):
         """ScsAmdStats of the workspace as a dict (cg_iters, lin_sys_solves, mat_vecs, ...)."""
         st = self._T.ScsAmdStats()

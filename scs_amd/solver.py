@@ -2,7 +2,7 @@
 
 Mirrors the reference project's Python interface (docs/src/api/python.rst in the
 reference tree: `scs.SCS(data, cone, **settings)`, `.solve(warm_start=True, x=None, y=None,
-s=None)`, `.update(b=None, c=None)`, result dict with 'x', 'y', 's', 'info') so that code
+s=None)`, `.update(b=None, c=None)` (here also `A=`, `P=`: new matrix values), result dict with 'x', 'y', 's', 'info') so that code
 written against `import scs` switches with `from scs_amd.solver import SCS`.  One ScsWork
 lives for the lifetime of the object (scs_init once, scs_solve / scs_update many times,
 scs_finish on close / garbage collection), exactly the workspace reuse the C API offers
@@ -73,12 +73,20 @@ class SCS:
         self._solved_once = True
         return {"x": self._x.copy(), "y": self._y.copy(), "s": self._s.copy(), "info": capi.info_dict(info)}
 
-    def update(self, b=None, c=None):
-        """scs_update: new right-hand side and / or cost on the same factorised workspace."""
+    def update(self, b=None, c=None, A=None, P=None):
+        """scs_update: new right-hand side and / or cost on the same workspace.  A / P (an extension, scs_amd_update_matrix): new VALUES
+        of the matrices on the pattern given at construction -- a scipy sparse matrix with exactly that pattern, or a 1-D array of the
+        values in its CSC order (P: upper triangle); the workspace is then what a new object on those matrices would hold, without the
+        pattern-dependent setup.  A different pattern or a non-finite value raises ValueError before the library is called."""
         if not self._w:
             raise RuntimeError("solver was closed")
         T = self._T
         f = T.np_float
+        ax = None if A is None else self._prob.values_of(A, "A")
+        px = None if P is None else self._prob.values_of(P, "P")
+        for v in (ax, px):
+            if v is not None and not np.all(np.isfinite(v)):
+                raise ValueError("matrix values must be finite")
         bp = cp = None
         if b is not None:
             self._b_new = np.ascontiguousarray(b, dtype=f)
@@ -90,8 +98,12 @@ class SCS:
             if self._c_new.shape != (self._prob.n,):
                 raise ValueError("c has the wrong length")
             cp = self._c_new.ctypes.data_as(T.fp)
-        if self._lib.scs_update(self._w, bp, cp) != 0:
+        if (bp is not None or cp is not None or (ax is None and px is None)) and self._lib.scs_update(self._w, bp, cp) != 0:
             raise RuntimeError("scs_update failed")
+        if ax is not None or px is not None:
+            if self._lib.scs_amd_update_matrix(self._w, ax.ctypes.data_as(T.fp) if ax is not None else None,
+                                               px.ctypes.data_as(T.fp) if px is not None else None) != 0:
+                raise RuntimeError("scs_amd_update_matrix failed")
 
     def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None):
         """scs_amd_solve_family: K problems that share A, P and the cones of this object and differ in (b, c), in one
