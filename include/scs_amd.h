@@ -385,6 +385,29 @@ scs_int scs_amd_linsys_multi_width(scs_int nrhs);
 scs_int scs_amd_linsys_mat_vec_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev);
 scs_int scs_amd_linsys_mul_a_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev);
 scs_int scs_amd_linsys_mul_at_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *Y_dev, scs_float *X_dev);
+/* ---- every column of a block under its own diag_r ----
+ * The block solve above shares the workspace's diag_r = [R_x; R_y] among its columns.  Here column k has its own R_x,k, R_y,k and
+ * its own Jacobi preconditioner: it computes what scs_update_lin_sys_diag_r(w, DR[:, k]) followed by
+ * scs_solve_lin_sys(w, B[:, k], S[:, k], tol[k]) computes (private.c:50-82, :106-119, :133-217, :284-327), while A and P are still
+ * read once per product for all columns -- a sweep over rho, scale or regularisation as one block.  Everything said above about
+ * independence, frozen columns, determinism and the statistics holds; with every column's R equal to the workspace's diag_r the
+ * call returns the bits and the iteration counts of scs_amd_solve_lin_sys_multi.  Three more blocks (2 n W + m W values) are
+ * allocated at the first per-column call and freed by scs_free_lin_sys_work; a caller who never makes one allocates nothing
+ * more than before. */
+/* K solves, column k under its own diag_r.  DR: host, column-major, (n + m) x nrhs, lddr >= n + m, column k = [R_x,k; R_y,k],
+ * every used entry finite and > 0; not modified.  Everything else as scs_amd_solve_lin_sys_multi.  The workspace's own diag_r is
+ * neither used nor changed.  More than 16 columns in chunks of at most 16; ONE column runs as a block of width 2 (it stays off
+ * the single-vector state).  -1 before any device call, B untouched: w / DR / B / tol NULL, nrhs < 1, lddr or ldb < n + m,
+ * lds < n with S, a non-finite or non-positive entry of DR, a row-sharded workspace.  -1 on a HIP failure with the stream
+ * drained (the convention of scs_amd_solve_lin_sys_multi); the workspace stays usable. */
+scs_int scs_amd_solve_lin_sys_multi_r(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr,
+                                      scs_float *B, scs_int ldb, const scs_float *S, scs_int lds,
+                                      const scs_float *tol, scs_int *iters);
+/* Y = R_x,k .* x_k + P x_k + A' R_y,k^-1 A x_k per column, on device blocks, the stream contract of
+ * scs_amd_linsys_mat_vec_multi_dev.  R_dev: (n + m) x W row-major, rows 0 .. n-1 = R_x, rows n .. n+m-1 = R_y; all W columns
+ * are read as ordinary columns (the caller fills padding columns, e.g. with 1).  -1 for nrhs outside 1 .. 16 (1 runs at W = 2). */
+scs_int scs_amd_linsys_mat_vec_multi_r_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *R_dev,
+                                           const scs_float *X_dev, scs_float *Y_dev);
 /* the SpMV kernel these entries (and scs_solve_lin_sys) run for A (which = 0) / A' (which = 1): the strings of
  * scs_amd_get_spmv_kernel_name.  Returns the length needed. */
 scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap);

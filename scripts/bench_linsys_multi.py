@@ -6,7 +6,13 @@ On the headline shape (n x 2n, 10 entries per column, the generator of scripts/b
   (ii) one block solve of K random columns at --tol against K successive scs_solve_lin_sys calls on the same columns.
 One JSON line per K: time per block product, time per column, its ratio to the single-vector product of the SAME run, the spread
 over the repeats, the algorithmic bytes of a block product (the entries of both orientations once, the vector traffic times K) and
-the share of the HBM peak that gives, and the per-column PCG iteration counts of both paths.  No pass mark: it reports."""
+the share of the HBM peak that gives, and the per-column PCG iteration counts of both paths.  No pass mark: it reports.
+
+--per-column-r: what it costs to give every column its own diag_r (scs_amd_linsys_mat_vec_multi_r_dev,
+scs_amd_solve_lin_sys_multi_r) against the shared-R block of the SAME run, the two alternated --reps times: the block product, the
+block solve (every column's R equal to the workspace's diag_r, so that both solves run the same iterations), and the one-off work
+of a per-column call -- upload and transposition of DR and the preconditioner pass -- as the difference of the two solve entries
+on an all-zero block (every column short-circuits: no iteration runs).  One JSON line per K; no pass mark here either."""
 import argparse
 import ctypes as C
 import json
@@ -80,6 +86,7 @@ def main():
     ap.add_argument("--ks", default="1,2,4,8,16")
     ap.add_argument("--no-solve", action="store_true")
     ap.add_argument("--lib", default="libscsamd_linsys.so")
+    ap.add_argument("--per-column-r", action="store_true", help="per-column diag_r against the shared-R block of the same run")
     a = ap.parse_args()
     n, m = a.n, a.m or 2 * a.n
     lib = capi.load(a.lib)
@@ -117,7 +124,67 @@ def main():
         lib.scs_amd_linsys_get_stats(w, C.byref(st))
         return st.cg_iters - before
 
-    for K in [int(v) for v in a.ks.split(",")]:
+    med = lambda v: float(np.median(v))
+    spread = lambda v: round((max(v) - min(v)) / med(v), 4)
+    for K in [int(v) for v in a.ks.split(",")] if a.per_column_r else []:
+        W = max(2, lib.scs_amd_linsys_multi_width(K))
+        xb, yb, rb = hip.malloc(n * W * sf), hip.malloc(n * W * sf), hip.malloc((n + m) * W * sf)
+        hip.put(xb, rng.uniform(-1, 1, n * W).astype(T.np_float))
+        R = np.ones((n + m, W), dtype=T.np_float)  # padding columns 1
+        R[:, :K] = dr[:, None] * rng.uniform(0.5, 2.0, K).astype(T.np_float)[None, :]
+        hip.put(rb, R)
+        percol_fn = lambda: lib.scs_amd_linsys_mat_vec_multi_r_dev(w, K, rb, xb, yb)
+        shared_fn = (lambda: lib.scs_amd_linsys_mat_vec_multi_dev(w, K, xb, yb)) if K > 1 else single_fn
+        assert percol_fn() == 0 and shared_fn() == 0
+        for _ in range(20):
+            percol_fn()
+            shared_fn()
+        tp, tsh = [], []
+        for _ in range(a.reps):  # alternated
+            tp.append(timed(percol_fn, a.calls, sync))
+            tsh.append(timed(shared_fn, a.calls, sync))
+        for d in (xb, yb, rb):
+            hip.free(d)
+        rec = dict(mode="per_column_r", K=K, width=W, n=n, m=m, nnz=int(A.nnz), calls=a.calls, reps=a.reps,
+                   percol_product_us=round(1e6 * med(tp), 2), shared_product_us=round(1e6 * med(tsh), 2),
+                   percol_over_shared=round(med(tp) / med(tsh), 4), percol_spread=spread(tp), shared_spread=spread(tsh),
+                   extra_MB_read=round((n + m) * (W - 1) * sf / 1e6, 1))
+        if not a.no_solve and K > 1:
+            B = np.asfortranarray(rng.uniform(-1, 1, (n + m, K)).astype(T.np_float))
+            DR = np.asfortranarray(np.tile(dr[:, None], (1, K)))
+            fp = lambda v: v.ctypes.data_as(T.fp)
+            it_p, it_s = np.zeros(K, dtype=T.np_int), np.zeros(K, dtype=T.np_int)
+
+            def solve(percol, rhs, tolv, it):
+                out = rhs.copy(order="F")
+                tv = np.full(K, tolv, dtype=T.np_float)
+                t0 = time.perf_counter()
+                if percol:
+                    rc = lib.scs_amd_solve_lin_sys_multi_r(w, K, fp(DR), n + m, fp(out), n + m, None, 0, fp(tv), it.ctypes.data_as(T.ip))
+                else:
+                    rc = lib.scs_amd_solve_lin_sys_multi(w, K, fp(out), n + m, None, 0, fp(tv), it.ctypes.data_as(T.ip))
+                dt = time.perf_counter() - t0
+                assert rc == 0
+                return dt, out
+
+            solve(True, B, 0.5, it_p)  # allocate the buffers of both paths outside the timed solves
+            solve(False, B, 0.5, it_s)
+            sp_, ss_, zp, zs = [], [], [], []
+            Z = np.zeros_like(B)
+            for _ in range(a.reps):  # alternated
+                dt, out_p = solve(True, B, a.tol, it_p)
+                sp_.append(dt)
+                dt, out_s = solve(False, B, a.tol, it_s)
+                ss_.append(dt)
+                zp.append(solve(True, Z, a.tol, np.zeros(K, dtype=T.np_int))[0])
+                zs.append(solve(False, Z, a.tol, np.zeros(K, dtype=T.np_int))[0])
+            rec.update(solve_percol_s=round(med(sp_), 4), solve_shared_s=round(med(ss_), 4), solve_percol_over_shared=round(med(sp_) / med(ss_), 4),
+                       solve_percol_spread=spread(sp_), solve_shared_spread=spread(ss_), iters_percol=[int(v) for v in it_p],
+                       iters_shared=[int(v) for v in it_s], same_bits=bool(np.array_equal(out_p, out_s)),
+                       zero_block_percol_ms=round(1e3 * med(zp), 3), zero_block_shared_ms=round(1e3 * med(zs), 3),
+                       r_setup_ms=round(1e3 * (med(zp) - med(zs)), 3))
+        print(json.dumps(rec), flush=True)
+    for K in [int(v) for v in a.ks.split(",")] if not a.per_column_r else []:
         W = lib.scs_amd_linsys_multi_width(K)
         xb = hip.malloc(n * W * sf)
         yb = hip.malloc(n * W * sf)

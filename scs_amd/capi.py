@@ -171,6 +171,11 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             fn = getattr(lib, nm)
             fn.restype = scs_int
             fn.argtypes = [C.c_void_p, scs_int, C.c_void_p, C.c_void_p]  # device pointers
+        # every column of a block under its own diag_r
+        lib.scs_amd_solve_lin_sys_multi_r.restype = scs_int
+        lib.scs_amd_solve_lin_sys_multi_r.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, fp, scs_int, fp, T.ip]
+        lib.scs_amd_linsys_mat_vec_multi_r_dev.restype = scs_int
+        lib.scs_amd_linsys_mat_vec_multi_r_dev.argtypes = [C.c_void_p, scs_int, C.c_void_p, C.c_void_p, C.c_void_p]  # device pointers
         lib.scs_amd_linsys_sync.restype = scs_int
         lib.scs_amd_linsys_sync.argtypes = [C.c_void_p]
         lib.scs_amd_linsys_spmv_kernel_name.restype = scs_int

@@ -58,6 +58,10 @@ struct MultiWork {
   DevBuf<real> part_pgp, part_ztr, part_max; // per-workgroup, per-column reduction partials
   DevBuf<CgCtlM> ctl;
   PinnedBuf<CgCtlM> hctl;
+  // per-column R (scs_amd_solve_lin_sys_multi_r): R_x, R_y and the Jacobi preconditioner of every column, 2 n W + m W values more.
+  // Allocated at the first per-column call only (ensure_multi_r): a caller who never makes one allocates what is listed above.
+  int rwidth = 0;           // width these three were allocated for (0: not allocated)
+  DevBuf<real> rxb, ryb, Mb; // n W, m W, n W
 };
 
 // ONE linear system split by rows of A over several devices (the operator split is
@@ -84,6 +88,9 @@ struct MultiRhs {
   int warm_cnt = 0;
   real warm_scale = 0;
   const int *pre_stopped = nullptr;
+  // every column under its own diag_r: R_x (n x W), R_y (m x W) and the preconditioner built from them by precond_multi_blocks
+  // (n x W); padding columns hold ordinary finite values (1).  All three or none; all null = the workspace's shared rx / ry / M.
+  const real *rx = nullptr, *ry = nullptr, *Minv = nullptr;
 };
 
 struct LinSys {
@@ -178,8 +185,14 @@ struct LinSys {
   // ---- blocks of right-hand sides (linsys_multi.h) ----
   MultiWork *multi = nullptr; // owned
   void ensure_multi(int W);
-  void launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip);
-  void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr);
+  void ensure_multi_r(int W); // ensure_multi plus the three R blocks of MultiWork
+  // dcol: e.d is a block (rows x W), one divisor / multiplier per column (EPI_DIV, EPI_GP, EPI_NEGDIV)
+  void launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
+                   bool dcol = false);
+  // rxb / ryb (both or neither): R_x / R_y per column as blocks instead of the workspace's own
+  void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr,
+                         const real *rxb = nullptr, const real *ryb = nullptr);
+  void precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv);
   void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
   void solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out);
   // ---- new values on the pattern given to init (scs_amd_linsys_update_values, include/scs_amd.h) ----

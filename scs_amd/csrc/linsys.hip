@@ -1839,9 +1839,10 @@ scs_int scs_solve_lin_sys(ScsLinSysWork *w, scs_float *b, const scs_float *s, sc
 // ---- blocks of right-hand sides: K solves of scs_solve_lin_sys (private.c:284-324) on one workspace ----
 scs_int scs_amd_linsys_multi_width(scs_int nrhs) { return (scs_int)multi_width((long long)nrhs); }
 
-scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B, scs_int ldb, const scs_float *S, scs_int lds,
-                                    const scs_float *tol, scs_int *iters) {
-  if (!w || !B || !tol || nrhs < 1) return -1;
+// the block solves of the host-pointer boundary.  DR == null: the columns share the workspace's diag_r
+// (scs_amd_solve_lin_sys_multi); else column k runs under column k of DR (scs_amd_solve_lin_sys_multi_r).
+static scs_int solve_multi_host(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
+                                const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
   LinSys &ls = w->ls;
   const size_t n = ls.n, m = ls.m, sz = sizeof(real);
   if ((long long)ldb < (long long)(n + m) || (S && (long long)lds < (long long)n)) return -1;
@@ -1852,25 +1853,46 @@ scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B
       const int K = (int)std::min<scs_int>(MULTI_W_MAX, nrhs - c0);
       scs_float *Bc = B + (size_t)c0 * (size_t)ldb;
       const scs_float *Sc = S ? S + (size_t)c0 * (size_t)lds : nullptr;
-      if (K == 1) { // the single-vector path, bit for bit
+      if (K == 1 && !DR) { // the single-vector path, bit for bit
         const int its = solve_one_host(ls, Bc, Sc, tol[c0]);
         if (iters) iters[c0] = its;
         continue;
       }
-      const int W = multi_width(K);
-      ls.ensure_multi(W);
+      const int W = K == 1 ? 2 : multi_width(K); // one column under its own R: a block of width 2, off the single-vector state
+      if (DR)
+        ls.ensure_multi_r(W);
+      else
+        ls.ensure_multi(W);
       MultiWork &mw = *ls.multi;
       const int g = ls.vec_grid((long long)(n + m));
+      if (DR) { // staged column-major in gt (B comes after it, in stream order); padding columns 1; then the preconditioner
+        HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, DR + (size_t)c0 * (size_t)lddr, (size_t)lddr * sz, (n + m) * sz, (size_t)K,
+                                   hipMemcpyHostToDevice, ls.stream));
+        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.rxb.p, (int)n,
+                                             mw.ryb.p, (int)m, K, (real)1));
+        ls.precond_multi_blocks(W, mw.rxb.p, mw.ryb.p, mw.Mb.p);
+      }
       if (Sc) { // staged column-major in z, transposed into s on the device
         HIP_CHECK(hipMemcpy2DAsync(mw.z.p, n * sz, Sc, (size_t)lds * sz, n * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
         MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.z.p, mw.s.p, (int)n,
-                                             (real *)nullptr, 0, K));
+                                             (real *)nullptr, 0, K, (real)0));
       }
       HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, Bc, (size_t)ldb * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
       MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
-                                           (int)m, K));
+                                           (int)m, K, (real)0));
       int its[MULTI_W_MAX];
-      ls.solve_multi_dev(K, W, Sc != nullptr, tol + c0, its);
+      if (DR) {
+        MultiRhs a;
+        a.bx = mw.bx.p;
+        a.by = mw.by.p;
+        a.s = Sc ? mw.s.p : nullptr;
+        a.rx = mw.rxb.p;
+        a.ry = mw.ryb.p;
+        a.Minv = mw.Mb.p;
+        ls.solve_multi_blocks(K, W, a, tol + c0, its);
+      } else {
+        ls.solve_multi_dev(K, W, Sc != nullptr, tol + c0, its);
+      }
       MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
                                            (int)m, K));
       HIP_CHECK(hipMemcpy2DAsync(Bc, (size_t)ldb * sz, mw.gt.p, (n + m) * sz, (n + m) * sz, (size_t)K, hipMemcpyDeviceToHost, ls.stream));
@@ -1885,6 +1907,26 @@ scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B
     return -1;
   }
   return 0;
+}
+
+scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B, scs_int ldb, const scs_float *S, scs_int lds,
+                                    const scs_float *tol, scs_int *iters) {
+  if (!w || !B || !tol || nrhs < 1) return -1;
+  return solve_multi_host(w, nrhs, nullptr, 0, B, ldb, S, lds, tol, iters);
+}
+
+// every column under its own diag_r (include/scs_amd.h); the checks come before any device call
+scs_int scs_amd_solve_lin_sys_multi_r(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
+                                      const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
+  if (!w || !DR || !B || !tol || nrhs < 1) return -1;
+  const long long len = (long long)w->ls.n + w->ls.m;
+  if (w->ls.shard || (long long)lddr < len || (long long)ldb < len) return -1;
+  for (scs_int k = 0; k < nrhs; ++k) {
+    const scs_float *d = DR + (size_t)k * (size_t)lddr;
+    for (long long i = 0; i < len; ++i)
+      if (!(std::isfinite((double)d[i]) && d[i] > 0)) return -1;
+  }
+  return solve_multi_host(w, nrhs, DR, lddr, B, ldb, S, lds, tol, iters);
 }
 
 scs_int scs_update_lin_sys_diag_r(ScsLinSysWork *w, const scs_float *new_diag_r) {
@@ -1981,6 +2023,25 @@ scs_int scs_amd_linsys_mul_at_multi_dev(ScsLinSysWork *w, scs_int nrhs, const sc
   return with_work_multi(w, nrhs, Y_dev, X_dev, [](LinSys &ls, int W, const real *y, real *x) {
     EpiArgs e{nullptr, nullptr, nullptr, nullptr};
     ls.launch_spmm(W, EPI_PLAIN, ls.At, y, x, e, nullptr, nullptr); }, [](LinSys &ls, const real *y, real *x) { ls.mul_At(y, x); });
+}
+// G X with R_x / R_y per column: R_dev = [R_x (n x W); R_y (m x W)] in the block layout; one column runs at width 2
+scs_int scs_amd_linsys_mat_vec_multi_r_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *R_dev, const scs_float *X_dev,
+                                           scs_float *Y_dev) {
+  if (!w || !R_dev || !X_dev || !Y_dev) return -1;
+  if (nrhs < 1 || nrhs > MULTI_W_MAX || w->ls.shard) return -1;
+  const int W = nrhs == 1 ? 2 : multi_width((long long)nrhs);
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    LinSys &ls = w->ls;
+    ls.ensure_multi(W);
+    const real *R = static_cast<const real *>(R_dev);
+    ls.mat_vec_multi_dev(W, static_cast<const real *>(X_dev), static_cast<real *>(Y_dev), nullptr, nullptr, nullptr, R, R + (size_t)ls.n * W);
+    HIP_CHECK(hipGetLastError());
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
 }
 // the SpMV kernel the workspace runs for A (which = 0) / A' (which = 1): the strings of scs_amd_get_spmv_kernel_name
 scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap) {

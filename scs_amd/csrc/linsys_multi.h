@@ -14,6 +14,13 @@
 //   k_m_cg_update   alpha; x, r, z; partials      k_m_cg_direction  stop tests; beta; p; control block
 // Buffers (MultiWork, linsys.h): 7 n W + 2 m W values at the largest width used (6 n W + 2 m W without P), allocated at the
 // first block call, reused, freed with the workspace.
+//
+// Per-column R (MultiRhs::rx / ry / Minv): column k runs under its own diag_r_k = [R_x,k; R_y,k] and its own Jacobi preconditioner
+// (k_m_precond), i.e. it computes what scs_update_lin_sys_diag_r(diag_r_k) followed by the single solve computes.  R_x, R_y and
+// M^-1 are then blocks in the block layout and the kernels that read them run in their per-column instantiation (the DCOL form of
+// csr_block_kernel, PERCOL of k_m_rhs_prep / k_m_cg_init / k_m_cg_update); A and P are still read once per product for all
+// columns.  The workspace's own rx, ry, M, captured graph and single-vector state are neither read nor written.  Three more blocks
+// (2 n W + m W values), allocated at the first per-column call only.
 #pragma once
 
 namespace scsamd {
@@ -22,14 +29,15 @@ struct TolArgs {
   real t[MULTI_W_MAX];
 };
 
-// column-major (len x K, leading dimension len) <-> block layout; padding columns become zero
+// column-major (len x K, leading dimension len) <-> block layout; padding columns become `fill` (0 for vectors; 1 for the R
+// blocks of a per-column solve, so that a padding column is an ordinary finite column)
 template <int W>
-__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_to_block(const real *__restrict__ src, real *dx, int n, real *dy, int m, int K) {
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_to_block(const real *__restrict__ src, real *dx, int n, real *dy, int m, int K, real fill) {
   const int len = n + m;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) {
     real *d = i < n ? dx + (size_t)i * W : dy + (size_t)(i - n) * W;
 #pragma unroll
-    for (int k = 0; k < W; ++k) d[k] = k < K ? src[(size_t)k * len + i] : (real)0;
+    for (int k = 0; k < W; ++k) d[k] = k < K ? src[(size_t)k * len + i] : fill;
   }
 }
 template <int W>
@@ -40,6 +48,28 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_from_block(real *dst, const 
 #pragma unroll
     for (int k = 0; k < W; ++k)
       if (k < K) dst[(size_t)k * len + i] = s[k];
+  }
+}
+
+// private.c:50-82 per column: the Jacobi preconditioner of column k under its own R_x,k / R_y,k, on blocks (rx, M: n x W; ry:
+// m x W).  Rows of CSR(A') with the lane mapping of the block product: W consecutive lanes serve one row, lane k column k; the
+// lanes of a row read the same val / idx (one broadcast read serves the W columns) and gather W contiguous values of ry.  Every
+// lane evaluates k_precond's expression in k_precond's order -- start from rx, the entries in index order, pdiag last, one
+// reciprocal -- so column k holds the bits k_precond gives for diag_r_k.  Rows are summed sequentially per lane, long ones too:
+// the kernel runs once per solve, not once per iteration.
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_precond(CsrView At, const real *__restrict__ rx, const real *__restrict__ ry,
+                                                            const real *__restrict__ pdiag, real *M) {
+  const size_t total = (size_t)At.rows * W;
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < total; f += (size_t)gridDim.x * blockDim.x) {
+    const int i = (int)(f / W), col = (int)(f & (W - 1));
+    real acc = rx[f];
+    for (eoff k = At.ptr[i]; k < At.ptr[i + 1]; ++k) {
+      const real a = At.val[k];
+      acc += a * a / ry[(size_t)At.idx[k] * W + col];
+    }
+    if (pdiag) acc += pdiag[i];
+    M[f] = (real)1 / acc;
   }
 }
 
@@ -73,7 +103,8 @@ __device__ __forceinline__ void set_all_done(CgCtlM *ctl, int W, bool col_done) 
 // `warm_part` (or null): per-workgroup, per-column |warm start|_inf partials; with it the tolerance of column k is formed here as
 // solve_dev forms it (src/scs.c:745-762), tol.t[k] being the cap.  `pre` (W ints, or null): columns that are stopped on entry --
 // nothing of theirs is read or written, here or by any later kernel of the solve, and they count no iteration.
-template <int W>
+// PERCOL: ry is an m x W block (every column its own R_y) instead of one vector of m.
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by, const real *__restrict__ ry, real *tmp, int n, int m,
                                                              const real *part, int pcount, CgCtlM *ctl, TolArgs tol, int K, int max_its,
                                                              const real *warm_part, int warm_cnt, real warm_scale, const int *pre) {
@@ -98,7 +129,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by,
       tmp[f] = 0;
     }
   } else {
-    for (size_t f = gtid; f < (size_t)m * W; f += gs) tmp[f] = by[f] / ry[f / W];
+    for (size_t f = gtid; f < (size_t)m * W; f += gs) tmp[f] = by[f] / ry[PERCOL ? f : f / W];
   }
   if (blockIdx.x == 0) {
     if (threadIdx.x < W) {
@@ -116,8 +147,8 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by,
   }
 }
 
-// private.c:145-172 per column
-template <int W>
+// private.c:145-172 per column.  PERCOL: M is an n x W block (every column its own preconditioner) instead of one vector of n.
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_init(real *x, const real *__restrict__ s, real *r, real *z, const real *__restrict__ M, int n,
                                                             real *part_ztr, real *part_max, const CgCtlM *ctl) {
   __shared__ real red[4 * W];
@@ -136,7 +167,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_init(real *x, const real 
         x[f] = 0;
       }
       r[f] = ri;
-      const real zi = ri * M[f / W];
+      const real zi = ri * M[PERCOL ? f : f / W];
       z[f] = zi;
       ztr += zi * ri;
       const real a = absval(ri);
@@ -177,8 +208,8 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_start(real *p, const real
   }
 }
 
-// private.c:181-197 per column
-template <int W>
+// private.c:181-197 per column; PERCOL as in k_m_cg_init
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_update(real *x, real *r, real *z, const real *__restrict__ p, const real *__restrict__ Gp,
                                                               const real *__restrict__ M, int n, const real *part_pgp, int cnt_pgp,
                                                               real *part_ztr, real *part_max, const CgCtlM *ctl, int parity) {
@@ -196,7 +227,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_update(real *x, real *r, 
       x[f] += alpha * p[f];
       const real ri = r[f] + (-alpha) * Gp[f];
       r[f] = ri;
-      const real zi = ri * M[f / W];
+      const real zi = ri * M[PERCOL ? f : f / W];
       z[f] = zi;
       ztr += zi * ri;
       const real a = absval(ri);
@@ -246,8 +277,17 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_direction(real *p, const 
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 template <int W>
-static void launch_spmm_w(int epi, int g, hipStream_t st, const CsrView &v, const real *X, real *Y, const EpiArgs &e, const int *cskip,
-                          const int *allskip) {
+static void launch_spmm_w(int epi, bool dcol, int g, hipStream_t st, const CsrView &v, const real *X, real *Y, const EpiArgs &e,
+                          const int *cskip, const int *allskip) {
+  if (dcol) { // e.d is a block: the per-column instantiations (the epilogues that have a d)
+    switch (epi) {
+    case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+    case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+    case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+    default: throw HipError("scs_amd: this block-product epilogue has no per-column form");
+    }
+    return;
+  }
   switch (epi) {
   case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
   case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
@@ -269,10 +309,11 @@ static void launch_spmm_w(int epi, int g, hipStream_t st, const CsrView &v, cons
     }                                                                                                                  \
   } while (0)
 
-void LinSys::launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip) {
+void LinSys::launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
+                         bool dcol) {
   const int g = spmm_grid(mat.rows, W);
   const CsrView v = mat.view();
-  MULTI_DISPATCH(W, launch_spmm_w<MW>(epi, g, stream, v, X, Y, e, cskip, allskip));
+  MULTI_DISPATCH(W, launch_spmm_w<MW>(epi, dcol, g, stream, v, X, Y, e, cskip, allskip));
   n_spmv++;
 }
 
@@ -299,18 +340,41 @@ void LinSys::ensure_multi(int W) {
   mw.width = W;
 }
 
-// G X on blocks (private.c:106-119 per column); dot_partials as in launch_spmm's EPI_GP
-void LinSys::mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip) {
+// The R blocks of the per-column solves at width W (2 n W + m W values): allocated by the first per-column call, so a caller who
+// never makes one holds what ensure_multi allocates and nothing more; freed with the workspace.
+void LinSys::ensure_multi_r(int W) {
+  ensure_multi(W);
+  MultiWork &mw = *multi;
+  if (mw.rwidth >= W) return;
+  mw.rwidth = 0;
+  mw.rxb.alloc((size_t)n * W);
+  mw.ryb.alloc((size_t)m * W);
+  mw.Mb.alloc((size_t)n * W);
+  mw.rwidth = W;
+}
+
+// Minv(n x W) = the Jacobi preconditioner of every column under its own rx (n x W) / ry (m x W): k_precond per column
+void LinSys::precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv) {
+  const CsrView v = At.view();
+  const real *pd = has_P ? Pdiag.p : nullptr;
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_precond<MW>, dim3(vec_grid((long long)n * W)), dim3(SCSAMD_BLOCK), 0, stream, v, rxb, ryb, pd, Minv));
+}
+
+// G X on blocks (private.c:106-119 per column); dot_partials as in launch_spmm's EPI_GP.  rxb / ryb (both or neither): R_x / R_y
+// per column as n x W / m x W blocks instead of the workspace's own.
+void LinSys::mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip, const real *rxb,
+                               const real *ryb) {
   MultiWork &mw = *multi;
   real *tmpb = mw.gt.p + (size_t)n * mw.width;
-  EpiArgs e1{ry.p, nullptr, nullptr, nullptr};
-  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip);
+  const bool percol = rxb != nullptr;
+  EpiArgs e1{percol ? ryb : ry.p, nullptr, nullptr, nullptr};
+  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip, percol);
   if (has_P) {
     EpiArgs ep{nullptr, nullptr, nullptr, nullptr};
     launch_spmm(W, EPI_PLAIN, P, X, mw.Pp.p, ep, cskip, allskip);
   }
-  EpiArgs e2{rx.p, X, has_P ? mw.Pp.p : nullptr, dot_partials};
-  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip);
+  EpiArgs e2{percol ? rxb : rx.p, X, has_P ? mw.Pp.p : nullptr, dot_partials};
+  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip, percol);
   n_matvecs++;
 }
 
@@ -328,6 +392,8 @@ void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *ite
 void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out) {
   MultiWork &mw = *multi;
   const bool warm = a.s != nullptr;
+  const bool percol = a.rx != nullptr; // every column under its own R_x / R_y / preconditioner: the workspace's rx, ry, M are not read
+  if (percol != (a.ry != nullptr) || percol != (a.Minv != nullptr)) throw HipError("scs_amd: per-column R needs rx, ry and Minv together");
   real *const bx = a.bx, *const by = a.by;
   const int gv = vec_grid((long long)n * W), gnm = vec_grid(((long long)n + m) * W);
   CgCtlM *c = mw.ctl.p;
@@ -340,15 +406,23 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
   const long long mv0 = n_matvecs;
 
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_absmax<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, nx, by, ny, mw.part_max.p));
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rhs_prep<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, ry.p, tmpb, n, m,
-                                       mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
+  if (percol)
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, true>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, a.ry, tmpb, n, m,
+                                         mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
+  else
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rhs_prep<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, ry.p, tmpb, n, m,
+                                         mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
   { // b_x += A' R_y^-1 r_y   (private.c:305)
     EpiArgs e{nullptr, nullptr, nullptr, nullptr};
     launch_spmm(W, EPI_ACC, At, tmpb, bx, e, zero, all);
   }
-  if (warm) mat_vec_multi_dev(W, a.s, mw.r.p, nullptr, zero, all); // r = G s  (private.c:153)
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_init<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
-                                       mw.z.p, M.p, n, mw.part_ztr.p, mw.part_max.p, c));
+  if (warm) mat_vec_multi_dev(W, a.s, mw.r.p, nullptr, zero, all, a.rx, a.ry); // r = G s  (private.c:153)
+  if (percol)
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_cg_init<MW, true>), dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
+                                         mw.z.p, a.Minv, n, mw.part_ztr.p, mw.part_max.p, c));
+  else
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_init<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
+                                         mw.z.p, M.p, n, mw.part_ztr.p, mw.part_max.p, c));
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_start<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                        mw.part_max.p, gv, c));
   // iteration batches: one control record read per batch, as solve_dev does with cg_pace=0 (every column's own count has to be
@@ -361,9 +435,13 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
     if (nb < 1) nb = 1;
     for (int j = 0; j < nb; ++j) {
       const int q = (int)((it + j) & 1);
-      mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all);
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_update<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p, Gp,
-                                           M.p, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
+      mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all, a.rx, a.ry);
+      if (percol)
+        MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_cg_update<MW, true>), dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p,
+                                             Gp, a.Minv, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
+      else
+        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_update<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p, Gp,
+                                             M.p, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
       MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_direction<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                            mw.part_max.p, gv, c, q));
     }
@@ -374,8 +452,8 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
     batch = std::max(4, std::min(mw.last_its / 4 + 1, 1024));
   }
   { // y = R_y^-1 (A x - r_y)   (private.c:313-317)
-    EpiArgs e{ry.p, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_NEGDIV, A, bx, by, e, zero, nullptr);
+    EpiArgs e{percol ? a.ry : ry.p, nullptr, nullptr, nullptr};
+    launch_spmm(W, EPI_NEGDIV, A, bx, by, e, zero, nullptr, percol);
   }
   HIP_CHECK(hipGetLastError());
   int most = 0;

@@ -101,7 +101,9 @@ template <int W> __device__ __forceinline__ real reduce_partials_col_max(const r
   return block_col_max<W>(s, sh);
 }
 
-// epilogues of spmv.h on element (r, col) of a block; d (R_x / R_y) is shared by the columns
+// epilogues of spmv.h on element (r, col) of a block.  DCOL = false: d (R_x / R_y) is shared by the columns, one value per row.
+// DCOL = true: every column has its own, d is a block in the block layout and element (r, col) is d[o] -- the W lanes of a group
+// read W contiguous values.  The choice is a template parameter: the shared form carries no test for the other.
 template <int EPI, int W>
 __device__ __forceinline__ real epi_init_blk(const EpiArgs &e, const real *y, size_t o) {
   if (EPI == EPI_GP) return e.y0 ? e.y0[o] : (real)0;
@@ -109,20 +111,21 @@ __device__ __forceinline__ real epi_init_blk(const EpiArgs &e, const real *y, si
   if (EPI == EPI_NEGDIV) return -y[o];
   return (real)0;
 }
-template <int EPI, int W>
+template <int EPI, int W, bool DCOL>
 __device__ __forceinline__ void epi_apply_blk(const EpiArgs &e, real *y, int r, size_t o, real acc, real &dot) {
   real out = acc;
-  if (EPI == EPI_DIV || EPI == EPI_NEGDIV) out = acc / e.d[r];
+  if (EPI == EPI_DIV || EPI == EPI_NEGDIV) out = acc / (DCOL ? e.d[o] : e.d[r]);
   if (EPI == EPI_GP) {
     const real xr = e.xin[o];
-    out = acc + e.d[r] * xr;
+    out = acc + (DCOL ? e.d[o] : e.d[r]) * xr;
     dot += xr * out;
   }
   y[o] = out;
 }
 
 // Y(rows x W) (op)= A X(cols x W).  EPI_GP: e.partial[blockIdx.x * W + k] receives the workgroup's part of column k's xin . y.
-template <int W, int EPI>
+// DCOL (EPI_DIV, EPI_GP, EPI_NEGDIV): e.d is a rows x W block, one divisor / multiplier per column (epi_apply_blk).
+template <int W, int EPI, bool DCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, const real *__restrict__ X, real *Y, EpiArgs e,
                                                                  const int *cskip, const int *allskip) {
   constexpr int G = SCSAMD_WAVE / W;
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
           acc += sval[k + 3] * x3;
         }
         for (; k < kz; ++k) acc += sval[k] * X[(size_t)sidx[k] * W + col];
-        epi_apply_blk<EPI, W>(e, Y, r, o, acc, dot);
+        epi_apply_blk<EPI, W, DCOL>(e, Y, r, o, acc, dot);
       }
       __builtin_amdgcn_wave_barrier();
       continue;
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
         acc += v3 * x3;
       }
       for (; k < z; ++k) acc += A.val[k] * X[(size_t)A.idx[k] * W + col];
-      epi_apply_blk<EPI, W>(e, Y, r, o, acc, dot);
+      epi_apply_blk<EPI, W, DCOL>(e, Y, r, o, acc, dot);
     }
     // long rows of this pass, one after the other, by the whole wave
     unsigned long long todo = __ballot(has && lng);
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
       if (on && g == gl) {
         const int rr = (int)(base + gl);
         const size_t o = (size_t)rr * W + col;
-        epi_apply_blk<EPI, W>(e, Y, rr, o, epi_init_blk<EPI, W>(e, Y, o) + part, dot);
+        epi_apply_blk<EPI, W, DCOL>(e, Y, rr, o, epi_init_blk<EPI, W>(e, Y, o) + part, dot);
       }
       todo &= ~((((unsigned long long)1 << W) - 1) << (gl * W));
     }

@@ -5,7 +5,8 @@ Solves the reduced KKT system of SCS on the GPU,
     (R_x + P + A' R_y^-1 A) x = r_x + A' R_y^-1 r_y ,   y = R_y^-1 (A x - r_y)
 
 for one right-hand side (`solve`, scs_solve_lin_sys) or for a block of them at once (`solve_many`,
-scs_amd_solve_lin_sys_multi: K independent PCG solves in lock step that share A, P and diag_r).  One workspace lives for the
+scs_amd_solve_lin_sys_multi: K independent PCG solves in lock step that share A, P and diag_r; with `diag_r=` every column
+runs under its own diag_r, scs_amd_solve_lin_sys_multi_r -- a sweep over rho, scale or regularisation as one block).  One workspace lives for the
 lifetime of the object (scs_init_lin_sys_work once, scs_free_lin_sys_work on close / garbage collection).  Host code only: every
 flop is in the library.
 
@@ -21,9 +22,10 @@ import numpy as np
 from . import capi
 
 
-def check_block(n, m, B, S=None, tol=1e-9):
+def check_block(n, m, B, S=None, tol=1e-9, DR=None):
     """Shapes of a block solve, checked before the library is called (needs no workspace): B (n + m, K), S None or (n, K),
-    tol a positive scalar or K of them.  Returns K."""
+    tol a positive scalar or K of them, DR None or (n + m, K) with every entry finite and positive (column k = the diag_r of
+    column k).  Returns K."""
     B = np.asarray(B)
     if B.ndim != 2 or B.shape[0] != n + m or B.shape[1] < 1:
         raise ValueError(f"B must have shape ({n + m}, K) with K >= 1, got {B.shape}")
@@ -37,6 +39,12 @@ def check_block(n, m, B, S=None, tol=1e-9):
         raise ValueError(f"tol must be a scalar or have length {K}, got shape {t.shape}")
     if not np.all(t > 0):
         raise ValueError("tol must be positive")
+    if DR is not None:
+        DR = np.asarray(DR)
+        if DR.ndim != 2 or DR.shape != (n + m, K):
+            raise ValueError(f"diag_r must have shape ({n + m}, {K}), got {DR.shape}")
+        if not (np.all(np.isfinite(DR)) and np.all(DR > 0)):
+            raise ValueError("diag_r must be finite and positive")
     return K
 
 
@@ -80,16 +88,28 @@ class LinSys:
             raise RuntimeError("scs_solve_lin_sys failed")
         return out
 
-    def solve_many(self, B, S=None, tol=1e-9):
+    def solve_many(self, B, S=None, tol=1e-9, diag_r=None):
         """scs_amd_solve_lin_sys_multi: column k of B (n + m, K) -> [x; y] of that column, as `solve` would give it; S (n, K) warm
         starts or None; tol a scalar or one per column.  Returns (XY, iters): the solutions (n + m, K) and the PCG iteration count
-        of every column.  B, S and tol are not modified."""
+        of every column.  diag_r (n + m, K): column k is solved under its own diag_r = diag_r[:, k], as `update_diag_r` followed by
+        `solve` would give it (scs_amd_solve_lin_sys_multi_r); the workspace's own diag_r is neither used nor changed.
+        B, S, tol and diag_r are not modified."""
         w, T = self._work(), self._T
-        K = check_block(self.n, self.m, B, S, tol)
+        K = check_block(self.n, self.m, B, S, tol, diag_r)
         out = np.array(B, dtype=T.np_float, order="F", copy=True)
         Sv = None if S is None else np.asfortranarray(S, dtype=T.np_float)
         tv = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, dtype=T.np_float), (K,)))
         iters = np.zeros(K, dtype=T.np_int)
+        if diag_r is not None:
+            Dv = np.asfortranarray(diag_r, dtype=T.np_float)
+            if not np.all(Dv > 0):  # an entry that underflows in the library's precision
+                raise ValueError("diag_r must be positive in the library's precision")
+            rc = self._lib.scs_amd_solve_lin_sys_multi_r(w, K, Dv.ctypes.data_as(T.fp), self.n + self.m, out.ctypes.data_as(T.fp),
+                                                         self.n + self.m, Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
+                                                         tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
+            if rc != 0:
+                raise RuntimeError("scs_amd_solve_lin_sys_multi_r failed")
+            return out, iters.astype(np.int64)
         rc = self._lib.scs_amd_solve_lin_sys_multi(w, K, out.ctypes.data_as(T.fp), self.n + self.m,
                                                    Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
                                                    tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
