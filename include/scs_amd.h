@@ -464,6 +464,28 @@ scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob,
                              ScsSolution *sols, ScsInfo *infos, /* nprob of each; sols[k].x/y/s caller-allocated */
                              scs_int warm_start);
 const char *scs_amd_solve_family_refusal(const ScsWork *w);
+/* ---- the same with a scale per problem, fixed or adaptive ----
+ * scs_amd_solve_family with one difference: the columns do not share diag_r.  Column k runs under its own
+ *   diag_r_k = [rho_x ; 1/(1000 scale_k) on the zero cone, 1/scale_k elsewhere ; TAU_FACTOR]   (src/scs.c:971-980)
+ * in every step that reads R: the block solve (its own R_x, R_y and Jacobi preconditioner, scs_amd_solve_lin_sys_multi_r), the
+ * glue of the iteration, the box cone's Newton iteration and the warm start (v_y = y + s / R_y,k).
+ * scales: nprob initial scales (host), or NULL for the workspace's stgs.scale in every column.  Every entry must be finite and
+ * > 0: otherwise SCS_FAILED before any device call, sols / infos untouched.
+ * adaptive_scale != 0: column k runs update_scale (src/scs.c:1164-1241) on its own residuals, with its own running sums and its
+ * own last update, where the single solve runs it -- at a convergence check, after the test, before the dual update.  A column
+ * whose scale changes gets its R, its preconditioner, its g = (R + M)^-1 [c_k; -b_k] (a cold solve to 1e-12 in which every other
+ * column is stopped on entry) and its v = rsk / R + 2 u_t - u anew; of a column whose scale did not change not one bit is read
+ * or written by that.  A frozen column never updates.  adaptive_scale == 0: the scales stay as given -- a scale sweep.
+ * With equal scales and adaptive_scale == 0 a column holds the bits scs_amd_solve_family gives on a workspace of that scale.
+ * infos[k].scale and infos[k].scale_updates are the column's own.  The workspace's stgs.scale, diag_r, the linear system's
+ * rx / ry / M, its captured graph and the single-solve state are neither read for the columns nor written: scs_solve and
+ * scs_amd_solve_family return the same bits before and after.  acceleration_lookback != 0 and log_csv_filename are refused as
+ * in scs_amd_solve_family (scs_amd_solve_family_scaled_refusal: that message, or NULL).  Holds one l x W and one n x W block
+ * more than scs_amd_solve_family (the R of every column and its preconditioner), allocated at the first scaled call.
+ * Everything else -- arguments, chunks, freezing, statuses, failure convention -- as in scs_amd_solve_family. */
+scs_int scs_amd_solve_family_scaled(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
+const char *scs_amd_solve_family_scaled_refusal(const ScsWork *w);
 /* What scs_init decided about its internal numbering (scs_amd/csrc/reorder.h: variables, the rows of the zero / nonnegative
  * cones and -- round 6 -- the rows behind the first one of a second-order cone may be renumbered so that the gathers of the CSR products of linsys/scs_matrix.c:161-186 share cache lines; callers never see
  * it -- b, c, warm starts and the returned (x, y, s) are mapped at this boundary).  out[0] = 1 if renumbered, out[1], out[2] =

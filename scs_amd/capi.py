@@ -217,6 +217,11 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
                                                  C.POINTER(T.ScsInfo), scs_int]
             lib.scs_amd_solve_family_refusal.restype = C.c_char_p
             lib.scs_amd_solve_family_refusal.argtypes = [C.c_void_p]
+            lib.scs_amd_solve_family_scaled.restype = scs_int
+            lib.scs_amd_solve_family_scaled.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, fp, C.POINTER(T.ScsSolution),
+                                                        C.POINTER(T.ScsInfo), scs_int]
+            lib.scs_amd_solve_family_scaled_refusal.restype = C.c_char_p
+            lib.scs_amd_solve_family_scaled_refusal.argtypes = [C.c_void_p]
             # a block of Anderson accelerations at once (include/scs_amd.h; scs_amd/accel.py is the object form)
             lib.scs_amd_aa_multi_width.restype = scs_int
             lib.scs_amd_aa_multi_width.argtypes = [scs_int]
@@ -489,6 +494,17 @@ def solve_family(lib, w, B, Cc, warm=None, warm_start=None):
     """scs_amd_solve_family on an initialised workspace `w`.  B (m x K), Cc (n x K): anything numpy turns into 2-D arrays;
     they are passed column-major.  warm: (X, Y, S) of shapes n x K, m x K, m x K, or None.  Returns (rc, list of K dicts
     in the shape of `solve`); the arrays of a refused call come back as they went in (zeros, or the warm start)."""
+    return _solve_family(lib, w, B, Cc, warm, warm_start, False, None)
+
+
+def solve_family_scaled(lib, w, B, Cc, scales=None, warm=None, warm_start=None):
+    """scs_amd_solve_family_scaled: solve_family with column k under its own scale.  scales: K initial scales, or None for the
+    workspace's scale in every column (passed as NULL).  A `scales` that is not K numbers raises ValueError before the library
+    is called."""
+    return _solve_family(lib, w, B, Cc, warm, warm_start, True, scales)
+
+
+def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales):
     T = lib._scs_types
     f = T.np_float
     B = np.asfortranarray(np.asarray(B, dtype=f))
@@ -508,5 +524,14 @@ def solve_family(lib, w, B, Cc, warm=None, warm_start=None):
         sols[k].y = C.cast(Y.ctypes.data + k * m * sz, T.fp)
         sols[k].s = C.cast(S.ctypes.data + k * m * sz, T.fp)
     ws = (1 if warm is not None else 0) if warm_start is None else int(warm_start)
-    rc = lib.scs_amd_solve_family(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos, ws)
+    if scaled:
+        sp = None
+        if scales is not None:
+            scales = np.ascontiguousarray(scales, dtype=f)
+            if scales.shape != (K,):
+                raise ValueError("scales must hold one scale per column of B")
+            sp = scales.ctypes.data_as(T.fp)
+        rc = lib.scs_amd_solve_family_scaled(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sp, sols, infos, ws)
+    else:
+        rc = lib.scs_amd_solve_family(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos, ws)
     return rc, [dict(x=X[:, k].copy(), y=Y[:, k].copy(), s=S[:, k].copy(), info=info_dict(infos[k])) for k in range(K)]

@@ -752,29 +752,41 @@ static int has_converged(const Resid &r, const ScsSettings &stgs, real nm_b_orig
   return 0;
 }
 
-static int update_scale(ScsWork *w, int iter) { // :1164-1241
-  const Resid &r = w->r_o;
-  const int since = iter - w->last_scale_update_iter;
+// The host law of update_scale (:1164-1241) for one problem: r its un-normalised residuals at `iter`, nm_b_orig / nm_c_orig its
+// |b|_inf, |c|_inf as given, `scale` its current scale, and its three running quantities.  Accumulates the log ratio; true when the
+// scale has to change, with *new_scale set and the running quantities reset (the caller counts the update and applies it).
+static bool scale_update_due(const Resid &r, real nm_b_orig, real nm_c_orig, real scale, int iter, real &sum_log_scale_factor,
+                             int &n_log_scale_factor, int &last_scale_update_iter, real *new_scale_out) {
+  const int since = iter - last_scale_update_iter;
   real denom_pri = std::max(r.nm_ax, r.nm_s);
-  denom_pri = std::max(denom_pri, w->nm_b_orig * r.tau);
+  denom_pri = std::max(denom_pri, nm_b_orig * r.tau);
   real rel_pri = safediv_pos(r.nm_ax_s_btau, denom_pri);
   real denom_dual = std::max(r.nm_px, r.nm_aty);
-  denom_dual = std::max(denom_dual, w->nm_c_orig * r.tau);
+  denom_dual = std::max(denom_dual, nm_c_orig * r.tau);
   real rel_dual = safediv_pos(r.nm_px_aty_ctau, denom_dual);
   rel_pri = std::max(rel_pri, (real)DIV_EPS_TOL);
   rel_dual = std::max(rel_dual, (real)DIV_EPS_TOL);
-  w->sum_log_scale_factor += std::log(rel_pri) - std::log(rel_dual);
-  w->n_log_scale_factor++;
-  const real factor = std::sqrt(std::exp(w->sum_log_scale_factor / (real)w->n_log_scale_factor));
-  if (since < RESCALING_MIN_ITERS) return 0;
-  const real new_scale =
-      std::min(std::max(w->stgs.scale * factor, (real)MIN_SCALE_VALUE), (real)MAX_SCALE_VALUE);
-  if (new_scale == w->stgs.scale) return 0;
+  sum_log_scale_factor += std::log(rel_pri) - std::log(rel_dual);
+  n_log_scale_factor++;
+  const real factor = std::sqrt(std::exp(sum_log_scale_factor / (real)n_log_scale_factor));
+  if (since < RESCALING_MIN_ITERS) return false;
+  const real new_scale = std::min(std::max(scale * factor, (real)MIN_SCALE_VALUE), (real)MAX_SCALE_VALUE);
+  if (new_scale == scale) return false;
   if (factor > std::sqrt((real)10.) || factor < (real)1. / std::sqrt((real)10.)) { // :1160-1162
+    sum_log_scale_factor = 0;
+    n_log_scale_factor = 0;
+    last_scale_update_iter = iter;
+    *new_scale_out = new_scale;
+    return true;
+  }
+  return false;
+}
+
+static int update_scale(ScsWork *w, int iter) { // :1164-1241
+  real new_scale;
+  if (scale_update_due(w->r_o, w->nm_b_orig, w->nm_c_orig, w->stgs.scale, iter, w->sum_log_scale_factor, w->n_log_scale_factor,
+                       w->last_scale_update_iter, &new_scale)) {
     w->scale_updates++;
-    w->sum_log_scale_factor = 0;
-    w->n_log_scale_factor = 0;
-    w->last_scale_update_iter = iter;
     w->stgs.scale = new_scale;
     set_diag_r(w);
     w->ls.set_diag_r_dev(w->diag_r.p);

@@ -3,7 +3,7 @@
 //
 // Column k is the map of reference src/scs.c:1356-1455 applied to problem k alone: its own tau, kappa, root_plus, scales of
 // normalize_b_c, g = (R + M)^-1 [c_k; -b_k], residuals, CG tolerance schedule (:745-762), convergence test, status and ScsInfo.
-// The columns share A, P, D, E, diag_r and the cone description and nothing else.  Every per-column reduction (|v|, the dots of
+// The columns share A, P, D, E, the cone description and -- in scs_amd_solve_family -- diag_r, and nothing else.  Every per-column reduction (|v|, the dots of
 // root_plus, the norms and inner products of populate_residuals) runs over the lanes and workgroup partials of one column only --
 // the fixed butterfly over the lanes of a column, the waves in wave order, one partial per workgroup and column re-reduced in
 // index order -- so within one width the bits of a column depend neither on its neighbours nor on its position.  No floating-point
@@ -20,8 +20,18 @@
 // block products (cskip of csr_block_kernel) and the block solve (pre_stopped of MultiRhs), and its slot of the cone block is
 // scratch.  Padding columns k >= K are frozen from the start and hold zeros.
 //
-// Refused: adaptive_scale (a scale update changes diag_r, which the columns share), acceleration_lookback (the Anderson memory is
-// per problem) and log_csv_filename.
+// Two entries, one loop.  scs_amd_solve_family: the columns share the workspace's diag_r (the instantiations with PERCOL / PC =
+// false).  scs_amd_solve_family_scaled: column k runs under its own diag_r_k, built from its own scale, in an l x W block R whose x
+// and y rows are the rx / ry blocks of the per-column block solve (MultiRhs::rx / ry / Minv, linsys_multi.h); the glue kernels read
+// R[f] where the shared form reads R[f / W], in the same expressions, so equal scales give the shared form's bits.  With
+// adaptive_scale the column runs update_scale (admm.hip, :1164-1241) on its own residuals where the single loop runs it -- at a
+// check, after the convergence test, before the dual update.  For the columns whose scale changed (FamCtl::upd), in this order:
+// their R (k_f_set_diag_r), the preconditioners (precond_multi_blocks) and the box cone's copy of r_y, their g (rebuilt and solved
+// cold to CG_BEST_TOL with every other column stopped on entry), their v (k_f_remap_v).  Of a column that did not update not one
+// bit is read or written by this, and a frozen column never updates.
+//
+// Refused: acceleration_lookback (the Anderson memory is per problem) and log_csv_filename; by scs_amd_solve_family also
+// adaptive_scale (a scale update changes diag_r, which its columns share).
 #pragma once
 
 namespace scsamd {
@@ -29,6 +39,10 @@ namespace scsamd {
 struct FamCtl {
   real ps[MULTI_W_MAX], ds[MULTI_W_MAX]; // primal_scale / dual_scale of normalize_b_c, per column
   int frozen[MULTI_W_MAX];               // non-zero: the column has finished (or is padding): nothing of it is read or written
+  // scs_amd_solve_family_scaled only: the column's own scale, and the columns whose scale has just been set (upd) or not (keep, the
+  // complement: what a block solve takes as pre_stopped).  Read by the kernels of a scale update and by nothing else.
+  real scale[MULTI_W_MAX];
+  int upd[MULTI_W_MAX], keep[MULTI_W_MAX];
 };
 
 // ----------------------------------------------------------------------------
@@ -47,7 +61,9 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_sumsq_partial(const real *__
 }
 
 // k_prep_linsys per column: normalize_v, u_t = [R_x v; -R_y v; v_tau], warm = u_x + tau g_x with its |.|_inf partials
-template <int W>
+// PERCOL (here and in the three kernels below that read R): R is an l x W block, every column its own diag_r, instead of one vector
+// of l -- R[f] where the shared form reads R[f / W], in the same expression: equal scales give the shared form's bits.
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_prep_linsys(real *v, real *u_t, const real *__restrict__ u, const real *__restrict__ g,
                                                                 const real *__restrict__ R, real *warm, int n, int l, const real *nrm_part,
                                                                 int nrm_cnt, real *warm_part, int do_normalize, const FamCtl *ctl) {
@@ -72,13 +88,13 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_prep_linsys(real *v, real *u
       }
       real ut;
       if (i < n) {
-        ut = vi * R[i];
+        ut = vi * R[PERCOL ? f : (size_t)i];
         const real w = u[f] + tau * g[f];
         warm[f] = w;
         const real a = absval(w);
         mx = a > mx ? a : mx;
       } else if (i < l - 1) {
-        ut = -vi * R[i];
+        ut = -vi * R[PERCOL ? f : (size_t)i];
       } else {
         ut = vi;
       }
@@ -90,7 +106,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_prep_linsys(real *v, real *u
 }
 
 // the five R-weighted dots of root_plus per column -> part[(q * stride + workgroup) * W + column]
-template <int W>
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_root_plus_partial(const real *__restrict__ p, const real *__restrict__ mu,
                                                                       const real *__restrict__ g, const real *__restrict__ R, int nm,
                                                                       real *part, int stride, const FamCtl *ctl) {
@@ -100,7 +116,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_root_plus_partial(const real
   if (!ctl->frozen[col]) {
     const size_t tot = (size_t)nm * W, gs = (size_t)gridDim.x * blockDim.x;
     for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
-      const real ri = R[f / W], gi = g[f], pi = p[f], mui = mu[f];
+      const real ri = R[PERCOL ? f : f / W], gi = g[f], pi = p[f], mui = mu[f];
       gg += gi * gi * ri;
       mug += mui * gi * ri;
       pg += pi * gi * ri;
@@ -124,7 +140,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_root_plus_partial(const real
 }
 
 // k_post_linsys per column: tau~, u_t -= tau~ g, u = 2 u_t - v, cw = -R_y (2 u_t - v)_y
-template <int W>
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_linsys(real *u_t, real *u, const real *__restrict__ v, const real *__restrict__ g,
                                                                 const real *__restrict__ R, real *cw, int n, int l, const real *part, int cnt,
                                                                 int stride, int feasible_iter, const FamCtl *ctl) {
@@ -140,7 +156,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_linsys(real *u_t, real 
     const real pp = reduce_partials_col_sum<W>(part + 3 * sw, cnt, red);
     const real pmu = reduce_partials_col_sum<W>(part + 4 * sw, cnt, red);
     if (on) {
-      const real tau_scale = R[l - 1], eta = v[(size_t)(l - 1) * W + col];
+      const real tau_scale = R[PERCOL ? (size_t)(l - 1) * W + col : (size_t)(l - 1)], eta = v[(size_t)(l - 1) * W + col];
       tau_t = root_plus_from_coeffs(tau_scale + gg, mug - 2 * pg - eta * tau_scale, pp - pmu);
     }
   }
@@ -153,7 +169,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_linsys(real *u_t, real 
       u_t[f] = ut;
       const real uu = 2 * ut - v[f];
       u[f] = uu;
-      if (i >= n) cw[f - nw] = uu * (-R[i]);
+      if (i >= n) cw[f - nw] = uu * (-R[PERCOL ? f : (size_t)i]);
     } else {
       u_t[f] = tau_t;
       const real uu = 2 * tau_t - v[f];
@@ -163,7 +179,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_linsys(real *u_t, real 
 }
 
 // k_post_cone per column: the Moreau post of the cone part, rsk = R (v + u - 2 u_t) and, with alpha > 0, v += alpha (u - u_t)
-template <int W>
+template <int W, bool PERCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_cone(real *u, const real *__restrict__ u_t, real *v, real *rsk,
                                                               const real *__restrict__ R, const real *__restrict__ cw, int n, int l,
                                                               real alpha, const FamCtl *ctl) {
@@ -172,7 +188,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_cone(real *u, const rea
   for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
     const int i = (int)(f / W);
     real ui = u[f];
-    const real ri = R[i];
+    const real ri = R[PERCOL ? f : (size_t)i];
     if (i >= n && i < l - 1) {
       ui = cw[f - nw] / ri + ui;
       u[f] = ui;
@@ -191,13 +207,46 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_dual_update(real *v, const r
   for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) v[f] += alpha * (u[f] - u_t[f]);
 }
 
-// g = [c; -b] per column
+// g = [c; -b] per column; skip (W ints): the columns that are left as they are
 template <int W>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_build_g(real *g, const real *__restrict__ c, const real *__restrict__ b, int n, int m,
-                                                            const FamCtl *ctl) {
-  if (ctl->frozen[threadIdx.x & (W - 1)]) return;
+                                                            const int *skip) {
+  if (skip[threadIdx.x & (W - 1)]) return;
   const size_t tot = (size_t)(n + m) * W, gs = (size_t)gridDim.x * blockDim.x, nw = (size_t)n * W;
   for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) g[f] = f < nw ? c[f] : -b[f - nw];
+}
+
+// ---- the kernels of a per-column scale (scs_amd_solve_family_scaled) ---------------------------------------------------------
+// k_set_diag_r on the l x W block, for the columns in ctl->upd only: diag_r_k = [rho_x; 1/(1000 scale_k) on the zero cone,
+// 1/scale_k elsewhere; TAU_FACTOR], in k_set_diag_r's expressions.  Padding columns (>= K) get R = 1, as the block solve's
+// per-column entry gives them: ordinary finite columns.
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_set_diag_r(real *R, int n, int m, int z, real rho_x, int K, const FamCtl *ctl) {
+  const int col = threadIdx.x & (W - 1);
+  if (!ctl->upd[col]) return;
+  const real scale = ctl->scale[col];
+  const int l = n + m + 1;
+  const size_t tot = (size_t)l * W, gs = (size_t)gridDim.x * blockDim.x;
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
+    const int i = (int)(f / W);
+    real r;
+    if (col >= K) r = (real)1;
+    else if (i < n) r = rho_x;
+    else if (i < n + z) r = (real)1.0 / ((real)1000. * scale);
+    else if (i < l - 1) r = (real)1.0 / scale;
+    else r = (real)TAU_FACTOR;
+    R[f] = r;
+  }
+}
+
+// k_remap_v on blocks, for the columns in ctl->upd only: v = rsk / R + 2 u_t - u after a scale update (:1236-1238)
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_remap_v(real *v, const real *__restrict__ rsk, const real *__restrict__ R,
+                                                            const real *__restrict__ u_t, const real *__restrict__ u, int l,
+                                                            const FamCtl *ctl) {
+  if (!ctl->upd[threadIdx.x & (W - 1)]) return;
+  const size_t tot = (size_t)l * W, gs = (size_t)gridDim.x * blockDim.x;
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) v[f] = rsk[f] / R[f] + 2 * u_t[f] - u[f];
 }
 
 // ---- residuals per column: the quantities Q_* of admm.hip -> part[(q * stride + workgroup) * W + column] --------------------
@@ -326,6 +375,10 @@ struct FamilyWork {
   DevBuf<FamCtl> ctl;
   PinnedBuf<FamCtl> hctl;
   std::vector<real> hblk, hblk2, col_x, col_y, col_s; // host staging
+  // scs_amd_solve_family_scaled only, allocated at its first call (family_ensure_r): every column its own diag_r
+  int rwidth = 0;
+  DevBuf<real> R;    // l x W: [R_x rows | R_y rows | the tau row]; its x and y parts are the rx / ry blocks MultiRhs takes
+  DevBuf<real> Minv; // n x W: the Jacobi preconditioner of every column under its own R (precond_multi_blocks)
 };
 static void family_free(FamilyWork *f) { delete f; }
 
@@ -335,6 +388,10 @@ struct FamCol {
   real ps = 1, ds = 1, nm_b_orig = 0, nm_c_orig = 0;
   int status = SCS_UNFINISHED, iter = 0;
   bool frozen = false;
+  // the scaled entry: the column's own scale and the state of its update_scale
+  real scale = 0, sum_log_scale_factor = 0;
+  int last_scale_update_iter = 0, n_log_scale_factor = 0, scale_updates = 0;
+  bool upd = false; // the scale has just been set: the next control record names the column in FamCtl::upd
 };
 
 static void family_ensure(ScsWork *w, int W) {
@@ -360,9 +417,20 @@ static void family_ensure(ScsWork *w, int W) {
   f.width = W;
 }
 
-// the message for a setting this entry refuses, or null (host only)
-static const char *family_refusal(const ScsWork *w) {
-  if (w->stgs.adaptive_scale) return "scs_amd_solve_family requires adaptive_scale == 0: a scale update changes diag_r, which the problems of a family share";
+// the R blocks of the scaled entry at width W (l W + n W values more): a caller who never makes a scaled call does not hold them
+static void family_ensure_r(ScsWork *w, int W) {
+  FamilyWork &f = *w->fam;
+  if (f.rwidth >= W) return;
+  f.rwidth = 0;
+  f.R.alloc((size_t)w->l * W);
+  f.Minv.alloc((size_t)w->n * W);
+  f.rwidth = W;
+}
+
+// the message for a setting the entry refuses, or null (host only).  scaled: scs_amd_solve_family_scaled, where every column has its
+// own diag_r and adaptive_scale is served
+static const char *family_refusal(const ScsWork *w, bool scaled = false) {
+  if (w->stgs.adaptive_scale && !scaled) return "scs_amd_solve_family requires adaptive_scale == 0: a scale update changes diag_r, which the problems of a family share";
   if (w->stgs.acceleration_lookback) return "scs_amd_solve_family requires acceleration_lookback == 0: Anderson acceleration is per problem";
   if (!w->log_csv_name.empty()) return "scs_amd_solve_family requires log_csv_filename == NULL: the per-iteration log describes one problem";
   return nullptr;
@@ -397,12 +465,16 @@ static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter) {
       fill_residuals(cols[k].r_n, cols[k].r_o, f.hq.p + k, W, iter, w->has_P, w->stgs.normalize != 0, cols[k].ps, cols[k].ds);
 }
 
-static void family_upload_ctl(ScsWork *w, int W, int K, const FamCol *cols) {
+// pad_upd: the padding columns count as just set too (the first record of a scaled chunk: their R becomes 1)
+static void family_upload_ctl(ScsWork *w, int W, int K, const FamCol *cols, int pad_upd = 0) {
   FamilyWork &f = *w->fam;
   for (int k = 0; k < MULTI_W_MAX; ++k) {
     f.hctl.p->ps[k] = k < K ? cols[k].ps : (real)1;
     f.hctl.p->ds[k] = k < K ? cols[k].ds : (real)1;
     f.hctl.p->frozen[k] = k < K && !cols[k].frozen ? 0 : 1;
+    f.hctl.p->scale[k] = k < K ? cols[k].scale : (real)1;
+    f.hctl.p->upd[k] = k < K ? (cols[k].upd ? 1 : 0) : pad_upd;
+    f.hctl.p->keep[k] = f.hctl.p->upd[k] ? 0 : 1;
   }
   // the pinned record is rewritten only after a synchronisation of the stream (every caller has just waited on it)
   HIP_CHECK(hipMemcpyAsync(f.ctl.p, f.hctl.p, sizeof(FamCtl), hipMemcpyHostToDevice, w->stream));
@@ -410,16 +482,23 @@ static void family_upload_ctl(ScsWork *w, int W, int K, const FamCol *cols) {
 
 // K (1 <= K <= W) problems as one block of width W.  B / Cc: column-major host data of this chunk.  Returns SCS_SIGINT when
 // interrupted (the unfinished columns are then filled by fail_out), 0 otherwise; throws on a HIP failure.
-static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, const real *Cc, size_t ldc, ScsSolution *sols,
-                        ScsInfo *infos, scs_int warm_start) {
+// PC = false: scs_amd_solve_family, the columns share the workspace's diag_r.  PC = true: scs_amd_solve_family_scaled, column k
+// runs under its own diag_r_k from scales[k] (null: the workspace's stgs.scale in every column) and, with adaptive_scale, under its
+// own update_scale; the workspace's diag_r and the linear system's rx / ry / M are not read.
+template <bool PC>
+static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, const real *Cc, size_t ldc, const real *scales,
+                        ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
   const int n = w->n, m = w->m, l = w->l;
   hipStream_t st = w->stream;
   const size_t nw = (size_t)n * W, mw = (size_t)m * W, lw = (size_t)l * W;
   family_ensure(w, W);
+  if (PC) family_ensure_r(w, W);
   w->ls.ensure_multi(W);
   w->cone.ensure_multi(W);
   w->cone.reset_multi_cold(); // every family solve starts its eigenbases and box Newton starts cold: reruns are bit-identical
   FamilyWork &f = *w->fam;
+  const real *const R = PC ? f.R.p : w->diag_r.p; // l x W block / one vector of l
+  const int gl = glue_grid((long long)l * W), gnm = glue_grid((long long)(n + m) * W);
   const double t0 = now_ms();
   double t_lin = 0;
   w->cone_timer.total_ms = 0;
@@ -450,14 +529,28 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   }
   f.b.upload(f.hblk.data(), mw, st);
   f.c.upload(f.hblk2.data(), nw, st);
-  family_upload_ctl(w, W, K, cols);
+  for (int k = 0; k < K; ++k) {
+    cols[k].scale = PC && scales ? scales[k] : w->stgs.scale;
+    cols[k].upd = PC;
+  }
+  family_upload_ctl(w, W, K, cols, PC ? 1 : 0);
+  // the R of every column (padding: 1), its preconditioner and the box cone's copy of its r_y
+  auto apply_scales = [&]() {
+    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_set_diag_r<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.R.p, n, m, (int)w->k.z, w->stgs.rho_x, K,
+                                       f.ctl.p));
+    w->ls.precond_multi_blocks(W, f.R.p, f.R.p + nw, f.Minv.p);
+    w->cone.set_multi_ry(f.R.p + nw, W);
+  };
+  if (PC) apply_scales();
+  for (int k = 0; k < K; ++k) cols[k].upd = false;
   HIP_CHECK(hipStreamSynchronize(st)); // the staging vectors are reused below
 
   // ---- solve_begin per column: warm / cold start (:660-687)
   f.hblk.assign(lw, (real)0);
   if (warm_start) {
-    std::vector<real> hr(l);
-    w->diag_r.download(hr.data(), l, st);
+    std::vector<real> hr(PC ? lw : (size_t)l); // PC: the R block, element (i, k) at i * W + k
+    if (PC) f.R.download(hr.data(), lw, st);
+    else w->diag_r.download(hr.data(), l, st);
     HIP_CHECK(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) {
       const ScsSolution &sol = sols[k];
@@ -477,7 +570,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       }
       for (int j = 0; j < n; ++j) f.hblk[(size_t)j * W + k] = x[j] != x[j] ? (real)0 : x[j];
       for (int i = 0; i < m; ++i) {
-        const real t = y[i] + s[i] / hr[n + i];
+        const real t = y[i] + s[i] / hr[PC ? (size_t)(n + i) * W + k : (size_t)(n + i)]; // the column's own R_y
         f.hblk[(size_t)(n + i) * W + k] = t != t ? (real)0 : t;
       }
     }
@@ -492,18 +585,20 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   HIP_CHECK(hipStreamSynchronize(st));
 
   // ---- update_work_cache per column: g = (R + M)^-1 [c; -b] to CG_BEST_TOL (:1118-1128)
-  const int gl = glue_grid((long long)l * W), gnm = glue_grid((long long)(n + m) * W);
   const int *frozen = f.ctl.p->frozen;
   real tolv[MULTI_W_MAX];
-  {
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.g.p, f.c.p, f.b.p, n, m, f.ctl.p));
+  // `skip` (W ints on the device): the columns whose g stays as it is -- not one bit of theirs is read or written
+  auto update_g = [&](const int *skip) {
+    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.g.p, f.c.p, f.b.p, n, m, skip));
     for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = (real)CG_BEST_TOL;
     MultiRhs a;
     a.bx = f.g.p;
     a.by = f.g.p + nw;
-    a.pre_stopped = frozen;
+    a.pre_stopped = skip;
+    if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
     w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
-  }
+  };
+  update_g(frozen);
 
   // ---- the loop of src/scs.c:1356-1455 on blocks
   real *part = f.part.p, *nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, *warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
@@ -513,7 +608,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   for (; i < max_iters && running > 0; ++i) {
     const int do_norm = i >= FEASIBLE_ITERS;
     if (do_norm) FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_prep_linsys<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, w->diag_r.p,
+    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
                                        f.warm.p, n, l, nrm_part, gl, warm_part, do_norm, f.ctl.p));
     { // the linear system (:763), every column on its own tolerance schedule (:745-762)
       const double tl = now_ms();
@@ -522,6 +617,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       a.by = f.u_t.p + nw;
       a.s = f.warm.p;
       a.pre_stopped = frozen;
+      if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
       if (w->cg_tol_override > 0) {
         for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
       } else {
@@ -535,17 +631,18 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     }
     const int feas = i < FEASIBLE_ITERS;
     if (!feas)
-      FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_root_plus_partial<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, w->diag_r.p,
+      FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
                                          n + m, part, PSTRIDE, f.ctl.p));
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_post_linsys<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, w->diag_r.p,
+    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
                                        f.cw.p, n, l, part, gnm, PSTRIDE, feas, f.ctl.p));
     int cslot = -1;
     if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
-    w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
+    if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true); // the box cone under the column's own r_y
+    else w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
     w->cone_timer.stop(cslot, st);
     w->cone_projs++;
     const bool check = i % CONVERGED_INTERVAL == 0;
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_post_cone<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, w->diag_r.p,
+    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
                                        f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
     if (!check) continue;
     if (interrupted()) { // :1400-1403
@@ -562,11 +659,35 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
         --running;
       }
     }
-    if (changed) family_upload_ctl(w, W, K, cols);
-    if (running == 0) break;
-    if (w->stgs.time_limit_secs && now_ms() - t0 > 1000. * w->stgs.time_limit_secs) {
+    if (running == 0) {
+      if (changed) family_upload_ctl(w, W, K, cols);
+      break;
+    }
+    const bool timed_out = w->stgs.time_limit_secs && now_ms() - t0 > 1000. * w->stgs.time_limit_secs;
+    // update_scale per running column, where the single loop runs it: after the convergence test, before the dual update (:1410-1412)
+    bool rescaled = false;
+    if (PC && w->stgs.adaptive_scale && !timed_out)
+      for (int k = 0; k < K; ++k) {
+        FamCol &c = cols[k];
+        if (c.frozen) continue;
+        real new_scale;
+        if (scale_update_due(c.r_o, c.nm_b_orig, c.nm_c_orig, c.scale, i, c.sum_log_scale_factor, c.n_log_scale_factor,
+                             c.last_scale_update_iter, &new_scale)) {
+          c.scale_updates++;
+          c.scale = new_scale;
+          c.upd = rescaled = true;
+        }
+      }
+    if (changed || rescaled) family_upload_ctl(w, W, K, cols); // one record: the pinned copy is rewritten after the next wait only
+    if (timed_out) {
       time_limit_reached = 1;
       break;
+    }
+    if (rescaled) { // update_scale's device half for the columns in upd; of the others not one bit changes
+      apply_scales();
+      update_g(f.ctl.p->keep);
+      FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
+      for (int k = 0; k < K; ++k) cols[k].upd = false;
     }
     FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
                                        f.ctl.p));
@@ -625,36 +746,41 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     info->status_val = cols[k].status;
     info->iter = cols[k].iter;
     info->setup_time = (real)w->setup_time;
-    info->scale = w->stgs.scale;
+    info->scale = PC ? cols[k].scale : w->stgs.scale;
+    info->scale_updates = cols[k].scale_updates;
     info->aa_stats.last_aa_norm = (real)NAN;
     const LoopEnd e{max_iters, time_limit_reached, false};
     finalize_status(cols[k].r_o, n, m, e, sol, info);
     info->solve_time = (real)solve_ms;
     info->lin_sys_time = (real)t_lin;
     info->cone_time = (real)cone_ms;
-    if (w->stgs.verbose) print_summary_row(cols[k].r_o, cols[k].iter, w->stgs.scale, (solve_ms + w->setup_time) / 1e3);
+    if (w->stgs.verbose) print_summary_row(cols[k].r_o, cols[k].iter, PC ? cols[k].scale : w->stgs.scale, (solve_ms + w->setup_time) / 1e3);
   }
   return sigint ? SCS_SIGINT : 0;
 }
 
-extern "C" {
-
-const char *scs_amd_solve_family_refusal(const ScsWork *w) { return w ? family_refusal(w) : nullptr; }
-
-scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
-                             ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+// the body of the two entries.  PC / scales: as in family_chunk; `name`: the entry, for the messages
+template <bool PC>
+static scs_int family_solve(const char *name, ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                            const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
   if (!w || !B || !Cc || !sols || !infos || nprob < 1) {
-    printf("ERROR: scs_amd_solve_family: missing ScsWork, B, Cc, ScsSolution or ScsInfo input, or nprob < 1\n");
+    printf("ERROR: %s: missing ScsWork, B, Cc, ScsSolution or ScsInfo input, or nprob < 1\n", name);
     return SCS_FAILED;
   }
   if ((long long)ldb < (long long)w->m || (long long)ldc < (long long)w->n) {
-    printf("ERROR: scs_amd_solve_family: ldb < m or ldc < n\n");
+    printf("ERROR: %s: ldb < m or ldc < n\n", name);
     return SCS_FAILED;
   }
-  if (const char *why = family_refusal(w)) {
+  if (const char *why = family_refusal(w, PC)) {
     printf("ERROR: %s\n", why);
     return SCS_FAILED;
   }
+  if (PC && scales)
+    for (scs_int k = 0; k < nprob; ++k)
+      if (!std::isfinite((double)scales[k]) || !(scales[k] > 0)) {
+        printf("ERROR: %s: scales[%li] must be a positive finite number\n", name, (long)k);
+        return SCS_FAILED;
+      }
   if (w->stale) { // the last scs_amd_update_matrix failed half way
     for (scs_int k = 0; k < nprob; ++k)
       fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
@@ -673,18 +799,35 @@ scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob, const scs_float *B, scs_
         continue;
       }
       const int W = std::max(2, multi_width(K)); // one problem runs as a block of width 2: it stays off the single-solve state
-      sigint = family_chunk(w, K, W, B + (size_t)done * (size_t)ldb, (size_t)ldb, Cc + (size_t)done * (size_t)ldc, (size_t)ldc,
-                            sols + done, infos + done, warm_start) == SCS_SIGINT;
+      sigint = family_chunk<PC>(w, K, W, B + (size_t)done * (size_t)ldb, (size_t)ldb, Cc + (size_t)done * (size_t)ldc, (size_t)ldc,
+                                PC && scales ? scales + done : nullptr, sols + done, infos + done, warm_start) == SCS_SIGINT;
     }
     if (w->stgs.verbose) print_rule();
   } catch (const std::exception &ex) {
     fprintf(stderr, "%s\n", ex.what());
     (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
-    for (scs_int k = 0; k < nprob; ++k)
-      fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, "HIP error in scs_amd_solve_family", "failure");
+    const std::string msg = std::string("HIP error in ") + name;
+    for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, msg.c_str(), "failure");
     return SCS_FAILED;
   }
   return 0;
+}
+
+extern "C" {
+
+const char *scs_amd_solve_family_refusal(const ScsWork *w) { return w ? family_refusal(w) : nullptr; }
+
+scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                             ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  return family_solve<false>("scs_amd_solve_family", w, nprob, B, ldb, Cc, ldc, nullptr, sols, infos, warm_start);
+}
+
+// every column under its own scale, fixed (adaptive_scale == 0: a scale sweep) or adapted by its own update_scale
+const char *scs_amd_solve_family_scaled_refusal(const ScsWork *w) { return w ? family_refusal(w, true) : nullptr; }
+
+scs_int scs_amd_solve_family_scaled(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  return family_solve<true>("scs_amd_solve_family_scaled", w, nprob, B, ldb, Cc, ldc, scales, sols, infos, warm_start);
 }
 
 } // extern "C"

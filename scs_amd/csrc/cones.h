@@ -21,6 +21,7 @@ struct ConeMulti {
   DevBuf<real> tile_part;      // per (tile, column)
   DevBuf<real> big_coef;       // per (big cone, column): [head, tail multiplier]
   DevBuf<real> box_t;          // W Newton warm starts
+  DevBuf<real> ry_cols;        // W columns of length m, column major: the box rows of a per-column r_y (set_multi_ry allocates it)
   DevBuf<int> psd_off, psd_k;  // tables of the LDS kernel, replicated per column
   DevBuf<real> psd_vprev, psd_tscratch; // per (column, block)
   std::vector<BigPsd *> big;   // per column: blocks beyond the LDS path
@@ -82,8 +83,12 @@ struct ConeDev {
   ConeMulti *multi = nullptr;
   void ensure_multi(int W);
   void proj_dual_multi(real *X, int W, int K, const real *r_y);
-  void proj_primal_multi(real *X, int W, int K, const real *r_y); // the same without the Moreau wrapper: Proj_K per column
-  void reset_multi_cold();                                        // box Newton starts and eigenbases of the block state: cold
+  // the same without the Moreau wrapper: Proj_K per column.  own_ry: every column under its own r_y (only the box cone reads it),
+  // column k's slice of the copy that set_multi_ry keeps; r_y is then not read
+  void proj_primal_multi(real *X, int W, int K, const real *r_y, bool own_ry = false);
+  // keeps a column-major copy of the box rows of the m x W block Ry; to be called again when Ry changes
+  void set_multi_ry(const real *Ry, int W);
+  void reset_multi_cold();                                       // box Newton starts and eigenbases of the block state: cold
   // launches shared by the two paths
   void launch_box(real *tx, real *t_warm, const real *rb);
   void launch_psd_lds(real *cw, int nblocks, const int *off, const int *kk, real *tscratch, real *vprev, int warm);

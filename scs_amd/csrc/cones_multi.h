@@ -22,6 +22,11 @@
 //   the box cone and PSD blocks beyond the LDS path: column after column, each on the state of its column position.
 // Carried state (Newton start of the box cone, eigenbases, the cold-restart counter) belongs to the column position at one width;
 // a change of width starts cold.  Nothing here reads or writes the state of the single-vector path.
+//
+// A column under its own r_y (proj_primal_multi's own_ry, for scs_amd_solve_family_scaled): only the box cone reads r_y inside the
+// projection, so set_multi_ry keeps a column-major copy of the box rows of an m x W block of r_y's and launch_box gets column k's
+// slice of it.  The public scs_amd_cone_proj_dual_multi keeps its one shared r_y: its Moreau passes would need the block as well,
+// and no caller asks for it.
 #pragma once
 
 namespace scsamd {
@@ -345,19 +350,32 @@ void ConeDev::reset_multi_cold() {
   for (BigPsd *b : mc.big) b->reset_warm_start();
 }
 
+// Ry (device, m x W block: every column its own r_y) -> the column-major copy of its box rows that launch_box takes a column of.
+// The copy lives with the block state of width W: a change of width (ensure_multi) drops it.
+void ConeDev::set_multi_ry(const real *Ry, int W) {
+  ensure_multi(W);
+  if (bsize <= 0) return;
+  ConeMulti &mc = *multi;
+  if (!mc.ry_cols.p) mc.ry_cols.alloc((size_t)m * W);
+  const int gb = std::max(1, std::min(2048, (bsize + CONE_TR - 1) / CONE_TR));
+  CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, Ry, mc.ry_cols.p, m, box_off, box_off + bsize));
+}
+
 // X (device, m x W block) <- Proj_K of its columns (proj_cone, cones.c:1340-1394, per column), without the Moreau wrapper: what
 // proj_primal is to proj_dual.  The elementwise and second-order passes run over all W columns; the box cone and the PSD blocks beyond
 // the LDS path over columns 0 .. K - 1.  Padding columns that hold zeros keep them.
-void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y) {
+void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y, bool own_ry) {
   ensure_multi(W);
   ConeMulti &mc = *multi;
+  if (own_ry && bsize > 0 && !mc.ry_cols.p) throw HipError("scs_amd: per-column r_y of the box cone has not been set");
   if (z + l > 0)
     CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_zero_pos<MW>, dim3(small_grid((long long)(z + l) * W)), dim3(SCSAMD_BLOCK), 0, stream, X, z, l));
   if (bsize > 0) { // column after column on the column position's Newton start
     const int gb = std::max(1, std::min(2048, (bsize + CONE_TR - 1) / CONE_TR));
     CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
     const real *rb = r_y ? r_y + box_off : (const real *)nullptr;
-    for (int k = 0; k < K; ++k) launch_box(mc.cols.p + (size_t)k * m + box_off, mc.box_t.p + k, rb);
+    for (int k = 0; k < K; ++k)
+      launch_box(mc.cols.p + (size_t)k * m + box_off, mc.box_t.p + k, own_ry ? mc.ry_cols.p + (size_t)k * m + box_off : rb);
     CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cols_to_rows<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
   }
   if (n_tiny)

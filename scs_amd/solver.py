@@ -105,12 +105,15 @@ class SCS:
                                                px.ctypes.data_as(T.fp) if px is not None else None) != 0:
                 raise RuntimeError("scs_amd_update_matrix failed")
 
-    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None):
+    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None, scale=None, own_scale=False):
         """scs_amd_solve_family: K problems that share A, P and the cones of this object and differ in (b, c), in one
         device-resident loop.  B: m x K, C: n x K, as arrays or as lists of K vectors.  With warm_start, x (n x K), y and
         s (m x K) seed the columns.  Returns a list of K dicts in the shape `solve` returns.  The object's own problem and
         its last solution are not touched.  Needs adaptive_scale=0, acceleration_lookback=0 and no log_csv_filename:
-        otherwise ValueError with the library's message."""
+        otherwise ValueError with the library's message.
+        own_scale=True (scs_amd_solve_family_scaled): every problem runs under its own scale and the object's adaptive_scale is
+        honoured, problem by problem; info["scale"] and info["scale_updates"] are the problem's own.  scale: K initial scales
+        (implies own_scale); without it every problem starts at the object's scale."""
         if not self._w:
             raise RuntimeError("solver was closed")
         m, n = self._prob.m, self._prob.n
@@ -128,7 +131,12 @@ class SCS:
         K = B.shape[1]
         if K < 1 or C_.shape[1] != K:
             raise ValueError("B and C must have the same number K >= 1 of columns")
-        why = self._lib.scs_amd_solve_family_refusal(self._w)
+        scaled = bool(own_scale) or scale is not None
+        if scale is not None:
+            scale = np.asarray(scale, dtype=float).reshape(-1)
+            if scale.shape[0] != K:
+                raise ValueError("scale must hold one initial scale per problem")
+        why = (self._lib.scs_amd_solve_family_scaled_refusal if scaled else self._lib.scs_amd_solve_family_refusal)(self._w)
         if why:
             raise ValueError(why.decode())
         warm = None
@@ -138,9 +146,12 @@ class SCS:
             warm = (block(x, n, "x"), block(y, m, "y"), block(s, m, "s"))
             if any(v.shape[1] != K for v in warm):
                 raise ValueError("warm-start blocks must have K columns")
-        rc, out = capi.solve_family(self._lib, self._w, B, C_, warm=warm)
+        if scaled:
+            rc, out = capi.solve_family_scaled(self._lib, self._w, B, C_, scales=scale, warm=warm)
+        else:
+            rc, out = capi.solve_family(self._lib, self._w, B, C_, warm=warm)
         if rc != 0:
-            raise RuntimeError("scs_amd_solve_family failed")
+            raise RuntimeError("scs_amd_solve_family_scaled failed" if scaled else "scs_amd_solve_family failed")
         return out
 
     def close(self):
