@@ -486,6 +486,49 @@ const char *scs_amd_solve_family_refusal(const ScsWork *w);
 scs_int scs_amd_solve_family_scaled(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
                                     const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
 const char *scs_amd_solve_family_scaled_refusal(const ScsWork *w);
+/* ---- a queue of problems through one block: the finished columns are refilled ----
+ * scs_amd_solve_family (own_scale == 0; scales must be NULL, adaptive_scale is refused) or scs_amd_solve_family_scaled
+ * (own_scale != 0; scales: nprob initial scales or NULL) for ANY nprob >= 1, through one block of `width` columns (2, 4, 8 or 16;
+ * 0: max(2, the block width of min(nprob, 16) columns)): a column that has ended gives its slot to the next problem of the queue
+ * while its neighbours run on, where the two entries above cut the queue into chunks that each wait for their slowest column.
+ * The schedule (part of the contract):
+ *  - one global iteration index i = 0, 1, 2, ...; a problem that starts at global iteration s runs its local iteration j = i - s,
+ *    and everything the loop derives from the iteration index it derives, per column, from j: the feasible first iteration, the
+ *    normalisation of v, the warm-start term 1 / (j + 1)^1.5 of the CG tolerance, the iteration of the residuals, of the
+ *    convergence test and of update_scale, and info.iter;
+ *  - problems 0 .. min(width, nprob) - 1 start at s = 0 in slots 0, 1, ...;
+ *  - a column ends at the bottom of global iteration i when j % 25 == 0 and its convergence test fires (iter = j), when
+ *    j + 1 == max_iters (iter = max_iters, its residuals evaluated after that iteration), or when at a check its own
+ *    time_limit_secs, counted from the moment its column started running, has passed;
+ *  - its result is then taken out and returned to sols[p] / infos[p] at once, and the lowest free slot takes the next problem of
+ *    the queue, in index order, which starts at the smallest multiple of 25 greater than i -- so all running columns reach their
+ *    checks in the same global iterations and one residual evaluation and one read-back serve all of them; the price is up to 24
+ *    block iterations in which the refilled slot does not run yet;
+ *  - the call ends when the queue is empty and every slot is free.
+ * The promise: for every problem p, (x, y, s), status_val, iter, scale, scale_updates and the residual and objective fields of
+ * ScsInfo are, bit for bit, what scs_amd_solve_family / scs_amd_solve_family_scaled returns for it in a call of the same width,
+ * whatever its place in the queue, the slot it gets and what its neighbours do.  With nprob <= width no slot is refilled.
+ * Refused (scs_amd_solve_family_stream_refusal(w, own_scale): the message, or NULL): what the entry of the chosen form refuses,
+ * and cones with PSD or complex PSD blocks (ssize + cssize > 0: the eigensolver's warm start and cold-restart counter belong to
+ * the width, not to a slot -- use the two entries above).  Refused arguments that depend on the workspace -- ldb < m, ldc < n,
+ * scales with own_scale == 0, a scale that is not finite and > 0 -- are reported by the same function until a call on the
+ * workspace is accepted.  Every refusal, and w, B, Cc, sols or infos NULL, nprob < 1 or a width outside {0, 2, 4, 8, 16} (checked
+ * before the workspace is looked at), returns SCS_FAILED with a message before any device call, with sols / infos untouched.
+ * infos[p].solve_time runs from the activation of p's column to its return; lin_sys_time is the block solves' wall time in
+ * between, cone_time the sampled mean of a block projection times p's iterations.  verbose prints one summary row per problem as
+ * it finishes.  SIGINT: the problems that run or have not started get SCS_SIGINT, the finished ones keep their results.  A HIP
+ * failure fails every problem of the call, those already returned included; the workspace stays usable.  The state of scs_solve
+ * and of the two entries above is not disturbed.  Holds W (l + 2 n + 3 m) values (the records of a column in and a column out) more than they do, from its first call on.
+ * scs_amd_family_stream_get_counters, for the last stream call on the workspace: out[0] block iterations (the last global i that
+ * ran, + 1), out[1] slot-iterations in which a column ran (a problem that converged with iter = j counts j + 1, one that ended at
+ * the cap max_iters), out[2] slot-iterations in which a slot held no running column (out[0] * width - out[1]), out[3] refills,
+ * out[4] residual evaluations, out[5] the width used. */
+scs_int scs_amd_solve_family_stream(ScsWork *w, scs_int nprob,
+                                    const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    scs_int own_scale, const scs_float *scales, scs_int width,
+                                    ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
+const char *scs_amd_solve_family_stream_refusal(const ScsWork *w, scs_int own_scale);
+void scs_amd_family_stream_get_counters(const ScsWork *w, long long out[6]);
 /* What scs_init decided about its internal numbering (scs_amd/csrc/reorder.h: variables, the rows of the zero / nonnegative
  * cones and -- round 6 -- the rows behind the first one of a second-order cone may be renumbered so that the gathers of the CSR products of linsys/scs_matrix.c:161-186 share cache lines; callers never see
  * it -- b, c, warm starts and the returned (x, y, s) are mapped at this boundary).  out[0] = 1 if renumbered, out[1], out[2] =

@@ -222,6 +222,13 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
                                                         C.POINTER(T.ScsInfo), scs_int]
             lib.scs_amd_solve_family_scaled_refusal.restype = C.c_char_p
             lib.scs_amd_solve_family_scaled_refusal.argtypes = [C.c_void_p]
+            lib.scs_amd_solve_family_stream.restype = scs_int
+            lib.scs_amd_solve_family_stream.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, scs_int, fp, scs_int,
+                                                        C.POINTER(T.ScsSolution), C.POINTER(T.ScsInfo), scs_int]
+            lib.scs_amd_solve_family_stream_refusal.restype = C.c_char_p
+            lib.scs_amd_solve_family_stream_refusal.argtypes = [C.c_void_p, scs_int]
+            lib.scs_amd_family_stream_get_counters.restype = None
+            lib.scs_amd_family_stream_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 6)]
             # a block of Anderson accelerations at once (include/scs_amd.h; scs_amd/accel.py is the object form)
             lib.scs_amd_aa_multi_width.restype = scs_int
             lib.scs_amd_aa_multi_width.argtypes = [scs_int]
@@ -504,7 +511,28 @@ def solve_family_scaled(lib, w, B, Cc, scales=None, warm=None, warm_start=None):
     return _solve_family(lib, w, B, Cc, warm, warm_start, True, scales)
 
 
-def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales):
+STREAM_WIDTHS = (0, 2, 4, 8, 16)
+
+
+def solve_family_stream(lib, w, B, Cc, width=0, own_scale=False, scales=None, warm=None, warm_start=None):
+    """scs_amd_solve_family_stream: any number K >= 1 of problems through one block of `width` columns (0: chosen from K), a
+    finished column's slot going to the next problem of the queue.  own_scale: scs_amd_solve_family_scaled's form, `scales` as
+    there; without it `scales` is passed on as given and the library refuses one.  A width outside STREAM_WIDTHS, a B / Cc that
+    are not m x K and n x K, or a `scales` that is not K numbers raise ValueError before the library is called."""
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or int(width) not in STREAM_WIDTHS:
+        raise ValueError("width must be 0, 2, 4, 8 or 16")
+    return _solve_family(lib, w, B, Cc, warm, warm_start, bool(own_scale), scales, stream_width=int(width))
+
+
+def family_stream_counters(lib, w):
+    """scs_amd_family_stream_get_counters of the last stream call on `w`: a dict of block_iters, run_slot_iters, idle_slot_iters,
+    refills, resid_evals, width"""
+    out = (C.c_longlong * 6)()
+    lib.scs_amd_family_stream_get_counters(w, C.byref(out))
+    return dict(zip(("block_iters", "run_slot_iters", "idle_slot_iters", "refills", "resid_evals", "width"), (int(v) for v in out)))
+
+
+def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales, stream_width=None):
     T = lib._scs_types
     f = T.np_float
     B = np.asfortranarray(np.asarray(B, dtype=f))
@@ -524,13 +552,16 @@ def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales):
         sols[k].y = C.cast(Y.ctypes.data + k * m * sz, T.fp)
         sols[k].s = C.cast(S.ctypes.data + k * m * sz, T.fp)
     ws = (1 if warm is not None else 0) if warm_start is None else int(warm_start)
-    if scaled:
-        sp = None
-        if scales is not None:
-            scales = np.ascontiguousarray(scales, dtype=f)
-            if scales.shape != (K,):
-                raise ValueError("scales must hold one scale per column of B")
-            sp = scales.ctypes.data_as(T.fp)
+    sp = None
+    if (scaled or stream_width is not None) and scales is not None:
+        scales = np.ascontiguousarray(scales, dtype=f)
+        if scales.shape != (K,):
+            raise ValueError("scales must hold one scale per column of B")
+        sp = scales.ctypes.data_as(T.fp)
+    if stream_width is not None:
+        rc = lib.scs_amd_solve_family_stream(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, 1 if scaled else 0, sp,
+                                             stream_width, sols, infos, ws)
+    elif scaled:
         rc = lib.scs_amd_solve_family_scaled(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sp, sols, infos, ws)
     else:
         rc = lib.scs_amd_solve_family(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos, ws)

@@ -32,6 +32,37 @@
 //
 // Refused: acceleration_lookback (the Anderson memory is per problem) and log_csv_filename; by scs_amd_solve_family also
 // adaptive_scale (a scale update changes diag_r, which its columns share).
+//
+// A third entry, the same loop with a phase per column.  scs_amd_solve_family_stream takes a queue of any length through the W
+// slots of ONE block: a column that has ended gives its slot to the next problem while its neighbours run on, where the two entries
+// above cut the queue into chunks that each wait for their slowest column.  The schedule (part of the contract; the tests replay it):
+//   * one global iteration index i = 0, 1, 2, ...; a problem that starts at global iteration s runs its local iteration j = i - s, and
+//     everything the loop derives from the iteration index it derives per column from j: the feasible first iteration
+//     (j < FEASIBLE_ITERS: tau = 1, u_tau = 1) and the normalisation of v (j >= FEASIBLE_ITERS) -- masks of columns in the PHASED
+//     instantiations of k_f_prep_linsys / k_f_post_linsys; the warm-start term 1 / (j + 1)^CG_RATE of the CG tolerance -- one factor
+//     per column (MultiRhs::warm_scale_col, k_m_rhs_prep's WS = TolArgs); the iteration passed to fill_residuals, has_converged and
+//     scale_update_due; info.iter;
+//   * problems 0 .. min(W, nprob) - 1 start at s = 0 in slots 0, 1, ...;
+//   * a column ends at the bottom of global iteration i when j % CONVERGED_INTERVAL == 0 and its test fires (iter = j, as the chunk
+//     loop freezes it), when j + 1 == max_iters (iter = max_iters; its residuals are evaluated then, for that column alone, as the
+//     chunk loop evaluates them after its last iteration), or when at a check its own time limit -- counted from the moment its
+//     column started running -- has passed;
+//   * its result is taken out (k_f_col_out: its x, y, s in one contiguous record, not the l x W blocks) and returned at once; the
+//     lowest free slot takes the next problem of the queue, in index order (k_f_col_in: its b, c, v and zeros in its u, u_t, rsk, cw,
+//     warm, g; its g from update_g with every other column skipped; with own scales its R, preconditioner and box r_y through the
+//     FamCtl::upd path of a scale update);
+//   * THAT PROBLEM STARTS AT THE SMALLEST MULTIPLE OF CONVERGED_INTERVAL GREATER THAN i, so every start is a multiple of 25: all
+//     running columns reach their checks in the same global iterations, one residual evaluation and one read-back serve all of
+//     them, and the tests of i % 25 in the loop stay global (k_f_post_cone's alpha among them).  The price is up to 24 block
+//     iterations in which the refilled slot is loaded but still frozen (it becomes a running column, frozen 1 -> 0, at the top of
+//     its start iteration: one wait and one control record, at most once per 25 iterations); a check phase per slot would cost up
+//     to W residual evaluations and synchronisations per 25 iterations and a per-column alpha instead;
+//   * the call ends when the queue is empty and every slot is free.  Iterations in which no column runs are not executed.
+// A refilled slot starts its box Newton iteration at 1 again (ConeDev::reset_multi_box_start, at its activation: while it waits its
+// part of the cone block is scratch like a frozen column's).  The other cones carried here keep no state between projections, and
+// PSD blocks are refused: the LDS eigensolver's warm flag is one per launch and its cold-restart counter belongs to the width.
+// Every problem that passes through a stream has, bit for bit, what the entry of the same form returns for it in a call of the
+// same width: the guarantee above (no dependence on neighbours or position) is what makes that an exact yardstick.
 #pragma once
 
 namespace scsamd {
@@ -63,7 +94,10 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_sumsq_partial(const real *__
 // k_prep_linsys per column: normalize_v, u_t = [R_x v; -R_y v; v_tau], warm = u_x + tau g_x with its |.|_inf partials
 // PERCOL (here and in the three kernels below that read R): R is an l x W block, every column its own diag_r, instead of one vector
 // of l -- R[f] where the shared form reads R[f / W], in the same expression: equal scales give the shared form's bits.
-template <int W, bool PERCOL = false>
+// PHASED (here and in k_f_post_linsys; scs_amd_solve_family_stream): the columns stand at different iterations of their own solves,
+// so the flag the loop derives from the iteration index -- do_normalize here, feasible_iter there -- is a mask, bit k for column k,
+// and a column whose bit equals the scalar form's flag runs the scalar form's expressions in the scalar form's order.
+template <int W, bool PERCOL = false, bool PHASED = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_prep_linsys(real *v, real *u_t, const real *__restrict__ u, const real *__restrict__ g,
                                                                 const real *__restrict__ R, real *warm, int n, int l, const real *nrm_part,
                                                                 int nrm_cnt, real *warm_part, int do_normalize, const FamCtl *ctl) {
@@ -71,9 +105,10 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_prep_linsys(real *v, real *u
   const int col = threadIdx.x & (W - 1);
   const bool on = !ctl->frozen[col];
   real factor = 1;
-  if (do_normalize) {
+  if (do_normalize) { // uniform over the workgroup: the reduction below synchronises it
     const real nrm = sqrt(reduce_partials_col_sum<W>(nrm_part, nrm_cnt, red));
-    if (nrm != (real)0) factor = sqrt((real)l) * (real)1. / nrm;
+    if (PHASED) do_normalize = (do_normalize >> col) & 1;
+    if (do_normalize && nrm != (real)0) factor = sqrt((real)l) * (real)1. / nrm;
   }
   real mx = 0;
   if (on) {
@@ -140,7 +175,9 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_root_plus_partial(const real
 }
 
 // k_post_linsys per column: tau~, u_t -= tau~ g, u = 2 u_t - v, cw = -R_y (2 u_t - v)_y
-template <int W, bool PERCOL = false>
+// PHASED: feasible_iter is a mask of the columns in their first iteration; `part` holds the dots of every running column (those of
+// a column in its first iteration are not used)
+template <int W, bool PERCOL = false, bool PHASED = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_linsys(real *u_t, real *u, const real *__restrict__ v, const real *__restrict__ g,
                                                                 const real *__restrict__ R, real *cw, int n, int l, const real *part, int cnt,
                                                                 int stride, int feasible_iter, const FamCtl *ctl) {
@@ -148,14 +185,15 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_post_linsys(real *u_t, real 
   const int col = threadIdx.x & (W - 1);
   const bool on = !ctl->frozen[col];
   real tau_t = 1;
-  if (!feasible_iter) {
+  if (PHASED || !feasible_iter) { // uniform over the workgroup: the reductions below synchronise it
     const size_t sw = (size_t)stride * W;
     const real gg = reduce_partials_col_sum<W>(part + 0 * sw, cnt, red);
     const real mug = reduce_partials_col_sum<W>(part + 1 * sw, cnt, red);
     const real pg = reduce_partials_col_sum<W>(part + 2 * sw, cnt, red);
     const real pp = reduce_partials_col_sum<W>(part + 3 * sw, cnt, red);
     const real pmu = reduce_partials_col_sum<W>(part + 4 * sw, cnt, red);
-    if (on) {
+    if (PHASED) feasible_iter = (feasible_iter >> col) & 1;
+    if (on && !feasible_iter) {
       const real tau_scale = R[PERCOL ? (size_t)(l - 1) * W + col : (size_t)(l - 1)], eta = v[(size_t)(l - 1) * W + col];
       tau_t = root_plus_from_coeffs(tau_scale + gg, mug - 2 * pg - eta * tau_scale, pp - pmu);
     }
@@ -214,6 +252,52 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_build_g(real *g, const real 
   if (skip[threadIdx.x & (W - 1)]) return;
   const size_t tot = (size_t)(n + m) * W, gs = (size_t)gridDim.x * blockDim.x, nw = (size_t)n * W;
   for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) g[f] = f < nw ? c[f] : -b[f - nw];
+}
+
+// ---- one column in, one column out (scs_amd_solve_family_stream) --------------------------------------------------------------
+// The columns named in `mask` (bit k: column k) are written from a column-major staging buffer: column k's record is the
+// `rec` = m + n + l values [b (m) | c (n) | v (l)] at stage + k * rec -- its normalised data and its start (warm or cold, tau row 1).
+// Its u, u_t, rsk, cw, warm and g become zero, as solve_begin leaves them.  Of a column outside the mask nothing is read or written.
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_col_in(const real *__restrict__ stage, unsigned mask, real *b, real *c, real *v,
+                                                           real *u, real *u_t, real *rsk, real *cw, real *warm, real *g, int n, int m) {
+  const int col = threadIdx.x & (W - 1);
+  if (!((mask >> col) & 1u)) return;
+  const int l = n + m + 1;
+  const real *sb = stage + (size_t)col * ((size_t)m + n + l), *sc = sb + m, *sv = sc + n;
+  const size_t tot = (size_t)l * W, gs = (size_t)gridDim.x * blockDim.x, nw = (size_t)n * W; // gs % W == 0: a lane stays in its column
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
+    const int i = (int)(f / W);
+    v[f] = sv[i];
+    u[f] = 0;
+    u_t[f] = 0;
+    rsk[f] = 0;
+    if (i < n) {
+      c[f] = sc[i];
+      warm[f] = 0;
+      g[f] = 0;
+    } else if (i < l - 1) {
+      b[f - nw] = sb[i - n];
+      cw[f - nw] = 0;
+      g[f] = 0;
+    }
+  }
+}
+
+// The result of the columns named in `mask`: column k's x and y rows of u and s rows of rsk -> the contiguous record of n + 2 m
+// values [x | y | s] at out + k * (n + 2 m), which is what the host downloads of a finished column.
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_col_out(real *out, unsigned mask, const real *__restrict__ u, const real *__restrict__ rsk,
+                                                            int n, int m) {
+  const int col = threadIdx.x & (W - 1);
+  if (!((mask >> col) & 1u)) return;
+  real *o = out + (size_t)col * ((size_t)n + 2 * (size_t)m);
+  const size_t tot = (size_t)(n + m) * W, gs = (size_t)gridDim.x * blockDim.x;
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
+    const size_t i = f / W;
+    o[i] = u[f];
+    if (i >= (size_t)n) o[i + m] = rsk[f];
+  }
 }
 
 // ---- the kernels of a per-column scale (scs_amd_solve_family_scaled) ---------------------------------------------------------
@@ -379,6 +463,12 @@ struct FamilyWork {
   int rwidth = 0;
   DevBuf<real> R;    // l x W: [R_x rows | R_y rows | the tau row]; its x and y parts are the rx / ry blocks MultiRhs takes
   DevBuf<real> Minv; // n x W: the Jacobi preconditioner of every column under its own R (precond_multi_blocks)
+  // scs_amd_solve_family_stream only, allocated at its first call (family_ensure_stream): the records of k_f_col_in / k_f_col_out,
+  // column k's at k * (m + n + l) / k * (n + 2 m), with their host copies, and the counters of the last stream call
+  int swidth = 0;
+  DevBuf<real> stage, outb;
+  std::vector<real> hstage, hout;
+  long long counters[6] = {0, 0, 0, 0, 0, 0};
 };
 static void family_free(FamilyWork *f) { delete f; }
 
@@ -392,6 +482,13 @@ struct FamCol {
   real scale = 0, sum_log_scale_factor = 0;
   int last_scale_update_iter = 0, n_log_scale_factor = 0, scale_updates = 0;
   bool upd = false; // the scale has just been set: the next control record names the column in FamCtl::upd
+  // the stream entry, where the record belongs to a slot and is reset when the slot is filled: the problem of the queue the slot
+  // holds (-1: none), the global iteration at which it starts (its local iteration is the global one minus this; 0 in a chunk),
+  // whether it is loaded but has not started yet, how it ended, and its own clocks
+  int prob = -1, start = 0;
+  bool pending = false;
+  int time_limit_reached = 0;
+  double t0 = 0, t_lin0 = 0;
 };
 
 static void family_ensure(ScsWork *w, int W) {
@@ -427,6 +524,17 @@ static void family_ensure_r(ScsWork *w, int W) {
   f.rwidth = W;
 }
 
+// the records of the stream entry at width W (W (l + 2 n + 3 m) values more: a record of m + n + l in, one of n + 2 m out, per column)
+static void family_ensure_stream(ScsWork *w, int W) {
+  FamilyWork &f = *w->fam;
+  if (f.swidth >= W) return;
+  f.swidth = 0;
+  const size_t n = w->n, m = w->m, l = w->l;
+  f.stage.alloc((m + n + l) * W);
+  f.outb.alloc((n + 2 * m) * W);
+  f.swidth = W;
+}
+
 // the message for a setting the entry refuses, or null (host only).  scaled: scs_amd_solve_family_scaled, where every column has its
 // own diag_r and adaptive_scale is served
 static const char *family_refusal(const ScsWork *w, bool scaled = false) {
@@ -437,7 +545,8 @@ static const char *family_refusal(const ScsWork *w, bool scaled = false) {
 }
 
 // one residual evaluation for all running columns, one read-back (populate_residuals on blocks)
-static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter) {
+// iter: the global iteration; column k is told its own, iter - cols[k].start.  only: the columns whose records are filled
+static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter, unsigned only = ~0u) {
   FamilyWork &f = *w->fam;
   const int n = w->n, m = w->m, l = w->l;
   hipStream_t st = w->stream;
@@ -461,8 +570,8 @@ static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter) {
   w->cone_timer.harvest(); // stream is idle here
   if (w->cone.n_psd > 0) w->psd_unconverged += w->cone.take_status(st);
   for (int k = 0; k < K; ++k)
-    if (!cols[k].frozen)
-      fill_residuals(cols[k].r_n, cols[k].r_o, f.hq.p + k, W, iter, w->has_P, w->stgs.normalize != 0, cols[k].ps, cols[k].ds);
+    if (!cols[k].frozen && ((only >> k) & 1u))
+      fill_residuals(cols[k].r_n, cols[k].r_o, f.hq.p + k, W, iter - cols[k].start, w->has_P, w->stgs.normalize != 0, cols[k].ps, cols[k].ds);
 }
 
 // pad_upd: the padding columns count as just set too (the first record of a scaled chunk: their R becomes 1)
@@ -476,8 +585,97 @@ static void family_upload_ctl(ScsWork *w, int W, int K, const FamCol *cols, int 
     f.hctl.p->upd[k] = k < K ? (cols[k].upd ? 1 : 0) : pad_upd;
     f.hctl.p->keep[k] = f.hctl.p->upd[k] ? 0 : 1;
   }
-  // the pinned record is rewritten only after a synchronisation of the stream (every caller has just waited on it)
+  // the pinned record is rewritten only after a synchronisation of the stream (every caller has just waited on it; the stream
+  // loop's activation of a loaded slot at the top of an iteration waits for exactly that)
   HIP_CHECK(hipMemcpyAsync(f.ctl.p, f.hctl.p, sizeof(FamCtl), hipMemcpyHostToDevice, w->stream));
+}
+
+// ---- the host arithmetic of one problem, shared by the chunk loop and the stream loop (staging: f.col_x / col_y / col_s) -----
+// scs_update (:1287-1325): renumber, the norms of the data as given, normalize_b_c with the problem's own sigma.  Leaves b in
+// f.col_y and c in f.col_x, in the internal numbering, and the problem's scales and norms in col.
+static void family_stage_data(ScsWork *w, const real *bk, const real *ck, FamCol &col) {
+  FamilyWork &f = *w->fam;
+  const int n = w->n, m = w->m;
+  const Reorder &ro = w->reord;
+  f.col_y.resize(m);
+  f.col_x.resize(n);
+  f.col_s.resize(m);
+  real *b = f.col_y.data(), *c = f.col_x.data();
+  for (int i = 0; i < m; ++i) b[i] = ro.active ? bk[ro.row_new2old[i]] : bk[i];
+  for (int j = 0; j < n; ++j) c[j] = ro.active ? ck[ro.col_new2old[j]] : ck[j];
+  real nb = 0, nc = 0;
+  for (int i = 0; i < m; ++i) nb = std::max(nb, (real)std::fabs(b[i]));
+  for (int j = 0; j < n; ++j) nc = std::max(nc, (real)std::fabs(c[j]));
+  col.nm_b_orig = nb;
+  col.nm_c_orig = nc;
+  if (w->stgs.normalize) col.ps = col.ds = normalize_b_c_sigma(w->scal, b, c);
+}
+
+// solve_begin's warm start (:660-687): v = [x; y + s / R_y] from the caller's (x, y, s), normalised with the problem's scales.
+// ry, ry_stride: the problem's own R_y, row i at ry[i * ry_stride].  Leaves the x part in f.col_x and the y part in f.col_y; false
+// (nothing written) when the caller gave no start for this problem.
+static bool family_stage_warm(ScsWork *w, const ScsSolution &sol, const FamCol &col, const real *ry, size_t ry_stride) {
+  if (!sol.x || !sol.y || !sol.s) return false;
+  FamilyWork &f = *w->fam;
+  const int n = w->n, m = w->m;
+  const Reorder &ro = w->reord;
+  real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
+  for (int j = 0; j < n; ++j) x[j] = ro.active ? sol.x[ro.col_new2old[j]] : sol.x[j];
+  for (int i = 0; i < m; ++i) {
+    y[i] = ro.active ? sol.y[ro.row_new2old[i]] : sol.y[i];
+    s[i] = ro.active ? sol.s[ro.row_new2old[i]] : sol.s[i];
+  }
+  if (w->stgs.normalize) { // normalize_sol (src/normalize.c:64-76) with the problem's scales
+    for (int j = 0; j < n; ++j) x[j] /= (w->scal.E[j] / col.ds);
+    for (int i = 0; i < m; ++i) {
+      y[i] /= (w->scal.D[i] / col.ps);
+      s[i] *= (w->scal.D[i] * col.ds);
+    }
+  }
+  for (int j = 0; j < n; ++j) x[j] = x[j] != x[j] ? (real)0 : x[j];
+  for (int i = 0; i < m; ++i) {
+    const real t = y[i] + s[i] / ry[(size_t)i * ry_stride];
+    y[i] = t != t ? (real)0 : t;
+  }
+  return true;
+}
+
+// solve_end / finalize: the problem's normalised (x, y, s) in f.col_x / col_y / col_s, in the internal numbering -> sol and info
+static void family_return(ScsWork *w, const FamCol &col, bool own_scale, int time_limit_reached, double solve_ms, double lin_ms,
+                          double cone_ms, ScsSolution *sol, ScsInfo *info) {
+  FamilyWork &f = *w->fam;
+  const int n = w->n, m = w->m;
+  const Reorder &ro = w->reord;
+  if (!sol->x) sol->x = (real *)calloc(n, sizeof(real));
+  if (!sol->y) sol->y = (real *)calloc(m, sizeof(real));
+  if (!sol->s) sol->s = (real *)calloc(m, sizeof(real));
+  real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
+  if (w->stgs.normalize) { // un_normalize_sol (src/normalize.c:78-91) with the problem's scales
+    for (int j = 0; j < n; ++j) x[j] *= (w->scal.E[j] / col.ds);
+    for (int r = 0; r < m; ++r) {
+      y[r] *= (w->scal.D[r] / col.ps);
+      s[r] /= (w->scal.D[r] * col.ds);
+    }
+  }
+  for (int j = 0; j < n; ++j) sol->x[ro.active ? ro.col_new2old[j] : j] = x[j];
+  for (int r = 0; r < m; ++r) {
+    sol->y[ro.active ? ro.row_new2old[r] : r] = y[r];
+    sol->s[ro.active ? ro.row_new2old[r] : r] = s[r];
+  }
+  memset(info, 0, sizeof *info);
+  strcpy(info->lin_sys_solver, scs_get_lin_sys_method());
+  info->status_val = col.status;
+  info->iter = col.iter;
+  info->setup_time = (real)w->setup_time;
+  info->scale = own_scale ? col.scale : w->stgs.scale;
+  info->scale_updates = col.scale_updates;
+  info->aa_stats.last_aa_norm = (real)NAN;
+  const LoopEnd e{(int)w->stgs.max_iters, time_limit_reached, false};
+  finalize_status(col.r_o, n, m, e, sol, info);
+  info->solve_time = (real)solve_ms;
+  info->lin_sys_time = (real)lin_ms;
+  info->cone_time = (real)cone_ms;
+  if (w->stgs.verbose) print_summary_row(col.r_o, col.iter, own_scale ? col.scale : w->stgs.scale, (solve_ms + w->setup_time) / 1e3);
 }
 
 // K (1 <= K <= W) problems as one block of width W.  B / Cc: column-major host data of this chunk.  Returns SCS_SIGINT when
@@ -503,29 +701,15 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   double t_lin = 0;
   w->cone_timer.total_ms = 0;
   w->cone_timer.samples = 0;
-  const bool nrm = w->stgs.normalize != 0;
-  const Reorder &ro = w->reord;
   FamCol cols[MULTI_W_MAX];
 
   // ---- scs_update per column (:1287-1325): renumber, norms of the data as given, normalize_b_c with the column's own sigma
   f.hblk.assign(mw, (real)0);
   f.hblk2.assign(nw, (real)0);
-  f.col_y.resize(m);
-  f.col_x.resize(n);
-  f.col_s.resize(m);
   for (int k = 0; k < K; ++k) {
-    const real *bk = B + (size_t)k * ldb, *ck = Cc + (size_t)k * ldc;
-    real *b = f.col_y.data(), *c = f.col_x.data();
-    for (int i = 0; i < m; ++i) b[i] = ro.active ? bk[ro.row_new2old[i]] : bk[i];
-    for (int j = 0; j < n; ++j) c[j] = ro.active ? ck[ro.col_new2old[j]] : ck[j];
-    real nb = 0, nc = 0;
-    for (int i = 0; i < m; ++i) nb = std::max(nb, (real)std::fabs(b[i]));
-    for (int j = 0; j < n; ++j) nc = std::max(nc, (real)std::fabs(c[j]));
-    cols[k].nm_b_orig = nb;
-    cols[k].nm_c_orig = nc;
-    if (nrm) cols[k].ps = cols[k].ds = normalize_b_c_sigma(w->scal, b, c);
-    for (int i = 0; i < m; ++i) f.hblk[(size_t)i * W + k] = b[i];
-    for (int j = 0; j < n; ++j) f.hblk2[(size_t)j * W + k] = c[j];
+    family_stage_data(w, B + (size_t)k * ldb, Cc + (size_t)k * ldc, cols[k]);
+    for (int i = 0; i < m; ++i) f.hblk[(size_t)i * W + k] = f.col_y[i];
+    for (int j = 0; j < n; ++j) f.hblk2[(size_t)j * W + k] = f.col_x[j];
   }
   f.b.upload(f.hblk.data(), mw, st);
   f.c.upload(f.hblk2.data(), nw, st);
@@ -553,26 +737,9 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     else w->diag_r.download(hr.data(), l, st);
     HIP_CHECK(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) {
-      const ScsSolution &sol = sols[k];
-      if (!sol.x || !sol.y || !sol.s) continue;
-      real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
-      for (int j = 0; j < n; ++j) x[j] = ro.active ? sol.x[ro.col_new2old[j]] : sol.x[j];
-      for (int i = 0; i < m; ++i) {
-        y[i] = ro.active ? sol.y[ro.row_new2old[i]] : sol.y[i];
-        s[i] = ro.active ? sol.s[ro.row_new2old[i]] : sol.s[i];
-      }
-      if (nrm) { // normalize_sol (src/normalize.c:64-76) with the column's scales
-        for (int j = 0; j < n; ++j) x[j] /= (w->scal.E[j] / cols[k].ds);
-        for (int i = 0; i < m; ++i) {
-          y[i] /= (w->scal.D[i] / cols[k].ps);
-          s[i] *= (w->scal.D[i] * cols[k].ds);
-        }
-      }
-      for (int j = 0; j < n; ++j) f.hblk[(size_t)j * W + k] = x[j] != x[j] ? (real)0 : x[j];
-      for (int i = 0; i < m; ++i) {
-        const real t = y[i] + s[i] / hr[PC ? (size_t)(n + i) * W + k : (size_t)(n + i)]; // the column's own R_y
-        f.hblk[(size_t)(n + i) * W + k] = t != t ? (real)0 : t;
-      }
+      if (!family_stage_warm(w, sols[k], cols[k], PC ? hr.data() + (size_t)n * W + k : hr.data() + n, PC ? W : 1)) continue; // its own R_y
+      for (int j = 0; j < n; ++j) f.hblk[(size_t)j * W + k] = f.col_x[j];
+      for (int i = 0; i < m; ++i) f.hblk[(size_t)(n + i) * W + k] = f.col_y[i];
     }
   }
   for (int k = 0; k < K; ++k) f.hblk[(size_t)(l - 1) * W + k] = 1;
@@ -720,41 +887,13 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       fail_out(w, m, n, sol, info, SCS_SIGINT, "interrupted", "interrupted");
       continue;
     }
-    if (!sol->x) sol->x = (real *)calloc(n, sizeof(real));
-    if (!sol->y) sol->y = (real *)calloc(m, sizeof(real));
-    if (!sol->s) sol->s = (real *)calloc(m, sizeof(real));
     real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
     for (int j = 0; j < n; ++j) x[j] = f.hblk[(size_t)j * W + k];
     for (int r = 0; r < m; ++r) {
       y[r] = f.hblk[(size_t)(n + r) * W + k];
       s[r] = f.hblk2[(size_t)r * W + k];
     }
-    if (nrm) { // un_normalize_sol (src/normalize.c:78-91) with the column's scales
-      for (int j = 0; j < n; ++j) x[j] *= (w->scal.E[j] / cols[k].ds);
-      for (int r = 0; r < m; ++r) {
-        y[r] *= (w->scal.D[r] / cols[k].ps);
-        s[r] /= (w->scal.D[r] * cols[k].ds);
-      }
-    }
-    for (int j = 0; j < n; ++j) sol->x[ro.active ? ro.col_new2old[j] : j] = x[j];
-    for (int r = 0; r < m; ++r) {
-      sol->y[ro.active ? ro.row_new2old[r] : r] = y[r];
-      sol->s[ro.active ? ro.row_new2old[r] : r] = s[r];
-    }
-    memset(info, 0, sizeof *info);
-    strcpy(info->lin_sys_solver, scs_get_lin_sys_method());
-    info->status_val = cols[k].status;
-    info->iter = cols[k].iter;
-    info->setup_time = (real)w->setup_time;
-    info->scale = PC ? cols[k].scale : w->stgs.scale;
-    info->scale_updates = cols[k].scale_updates;
-    info->aa_stats.last_aa_norm = (real)NAN;
-    const LoopEnd e{max_iters, time_limit_reached, false};
-    finalize_status(cols[k].r_o, n, m, e, sol, info);
-    info->solve_time = (real)solve_ms;
-    info->lin_sys_time = (real)t_lin;
-    info->cone_time = (real)cone_ms;
-    if (w->stgs.verbose) print_summary_row(cols[k].r_o, cols[k].iter, PC ? cols[k].scale : w->stgs.scale, (solve_ms + w->setup_time) / 1e3);
+    family_return(w, cols[k], PC, time_limit_reached, solve_ms, t_lin, cone_ms, sol, info);
   }
   return sigint ? SCS_SIGINT : 0;
 }
@@ -813,7 +952,373 @@ static scs_int family_solve(const char *name, ScsWork *w, scs_int nprob, const s
   return 0;
 }
 
+// ============================================================================
+// scs_amd_solve_family_stream: a queue of problems through the W slots of one block (the schedule: the header comment)
+// ============================================================================
+static const char *family_stream_refusal(const ScsWork *w, bool own_scale) {
+  if (const char *why = family_refusal(w, own_scale)) return why;
+  if (w->k.ssize + w->k.cssize > 0)
+    return "scs_amd_solve_family_stream requires cones without PSD blocks (ssize + cssize == 0): the warm start and the cold-restart counter of "
+           "the LDS eigensolver belong to the width, not to a slot; use scs_amd_solve_family or scs_amd_solve_family_scaled";
+  return nullptr;
+}
+
+// The loop.  returned[p] != 0: problem p has its result in sols[p] / infos[p].  Throws on a HIP failure; true when interrupted
+// (the problems not yet returned are then left to the caller).
+template <bool PC>
+static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_t ldb, const real *Cc, size_t ldc, const real *scales,
+                              ScsSolution *sols, ScsInfo *infos, scs_int warm_start, std::vector<char> &returned) {
+  const int n = w->n, m = w->m, l = w->l;
+  hipStream_t st = w->stream;
+  const size_t nw = (size_t)n * W, lw = (size_t)l * W;
+  const int K = std::min(W, nprob); // slots in use; columns K .. W - 1 are padding: frozen and zero throughout
+  family_ensure(w, W);
+  if (PC) family_ensure_r(w, W);
+  family_ensure_stream(w, W);
+  w->ls.ensure_multi(W);
+  w->cone.ensure_multi(W);
+  w->cone.reset_multi_cold();
+  FamilyWork &f = *w->fam;
+  long long *cnt = f.counters;
+  for (int q = 0; q < 6; ++q) cnt[q] = 0;
+  cnt[5] = W;
+  const real *const R = PC ? f.R.p : w->diag_r.p;
+  const int gl = glue_grid((long long)l * W), gnm = glue_grid((long long)(n + m) * W);
+  w->cone_timer.total_ms = 0;
+  w->cone_timer.samples = 0;
+  const size_t rec_in = (size_t)m + n + l, rec_out = (size_t)n + 2 * (size_t)m;
+  f.hstage.assign(rec_in * W, (real)0);
+  f.hout.assign(rec_out * W, (real)0);
+  FamCol cols[MULTI_W_MAX];
+  for (FamCol &c : cols) c.frozen = true; // an empty slot
+  std::vector<real> hr;                   // R_y for the warm starts: the shared diag_r once, the R block at every warm fill
+  const int *frozen = f.ctl.p->frozen;
+  real tolv[MULTI_W_MAX], wsc[MULTI_W_MAX];
+  const int max_iters = (int)w->stgs.max_iters;
+  double t_lin = 0;
+  int next = 0, busy = 0, running = 0; // the queue's head; slots that hold a problem; slots whose column runs
+
+  auto apply_scales = [&]() {
+    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_set_diag_r<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.R.p, n, m, (int)w->k.z, w->stgs.rho_x, K,
+                                       f.ctl.p));
+    w->ls.precond_multi_blocks(W, f.R.p, f.R.p + nw, f.Minv.p);
+    w->cone.set_multi_ry(f.R.p + nw, W);
+  };
+  auto update_g = [&](const int *skip) {
+    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.g.p, f.c.p, f.b.p, n, m, skip));
+    for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = (real)CG_BEST_TOL;
+    MultiRhs a;
+    a.bx = f.g.p;
+    a.by = f.g.p + nw;
+    a.pre_stopped = skip;
+    if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
+    w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
+  };
+
+  // The lowest free slots take the next problems of the queue, which start at global iteration `start`.  The stream is idle on
+  // entry (the control record is rewritten) and has been waited on after the staging upload on return (update_g waits).
+  auto fill = [&](int start, bool first) {
+    unsigned mask = 0;
+    for (int k = 0; k < K && next < nprob; ++k) {
+      if (cols[k].prob >= 0) continue;
+      FamCol &c = cols[k] = FamCol();
+      c.prob = next++;
+      c.start = start;
+      c.frozen = c.pending = !first; // the first columns run from iteration 0: nothing to wait for
+      c.upd = true;                  // its R (PC) and its g are built below, with every other column left as it is
+      c.scale = PC && scales ? scales[c.prob] : w->stgs.scale;
+      family_stage_data(w, B + (size_t)c.prob * ldb, Cc + (size_t)c.prob * ldc, c);
+      real *rec = f.hstage.data() + (size_t)k * rec_in;
+      std::copy(f.col_y.begin(), f.col_y.end(), rec);
+      std::copy(f.col_x.begin(), f.col_x.end(), rec + m);
+      std::fill(rec + m + n, rec + rec_in, (real)0);
+      rec[rec_in - 1] = 1; // the tau row of v
+      mask |= 1u << k;
+      ++busy;
+      if (first) {
+        ++running;
+        c.t0 = now_ms();
+      } else {
+        ++cnt[3];
+      }
+    }
+    if (!mask) return;
+    family_upload_ctl(w, W, K, cols, first && PC ? 1 : 0);
+    if (PC) apply_scales();
+    if (warm_start) { // solve_begin per problem, under its own R_y
+      if (PC || hr.empty()) {
+        hr.resize(PC ? lw : (size_t)l);
+        if (PC) f.R.download(hr.data(), lw, st);
+        else w->diag_r.download(hr.data(), l, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+      }
+      for (int k = 0; k < K; ++k) {
+        if (!((mask >> k) & 1u)) continue;
+        if (!family_stage_warm(w, sols[cols[k].prob], cols[k], PC ? hr.data() + nw + k : hr.data() + n, PC ? W : 1)) continue;
+        real *v = f.hstage.data() + (size_t)k * rec_in + m + n;
+        std::copy(f.col_x.begin(), f.col_x.end(), v);
+        std::copy(f.col_y.begin(), f.col_y.end(), v + n);
+      }
+    }
+    for (int k = 0; k < K; ++k)
+      if ((mask >> k) & 1u) HIP_CHECK(hipMemcpyAsync(f.stage.p + (size_t)k * rec_in, f.hstage.data() + (size_t)k * rec_in, rec_in * sizeof(real),
+                                                     hipMemcpyHostToDevice, st));
+    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_col_in<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.stage.p, mask, f.b.p, f.c.p, f.v.p, f.u.p,
+                                       f.u_t.p, f.rsk.p, f.cw.p, f.warm.p, f.g.p, n, m));
+    update_g(first ? frozen : f.ctl.p->keep); // update_work_cache for the new columns alone (:1118-1128)
+    for (int k = 0; k < K; ++k) cols[k].upd = false;
+  };
+
+  // The columns in `mask` have ended: their (x, y, s) out of the blocks, their results to the caller, their slots free.
+  auto take_out = [&](unsigned mask) {
+    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_col_out<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.outb.p, mask, f.u.p, f.rsk.p, n, m));
+    for (int k = 0; k < K; ++k)
+      if ((mask >> k) & 1u) HIP_CHECK(hipMemcpyAsync(f.hout.data() + (size_t)k * rec_out, f.outb.p + (size_t)k * rec_out, rec_out * sizeof(real),
+                                                     hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    w->cone_timer.harvest();
+    const double t1 = now_ms();
+    const double cone_iter_ms = w->cone_timer.samples ? w->cone_timer.total_ms / (double)w->cone_timer.samples : 0.0; // sampled mean
+    for (int k = 0; k < K; ++k) {
+      if (!((mask >> k) & 1u)) continue;
+      FamCol &c = cols[k];
+      const real *rec = f.hout.data() + (size_t)k * rec_out;
+      std::copy(rec, rec + n, f.col_x.begin());
+      std::copy(rec + n, rec + n + m, f.col_y.begin());
+      std::copy(rec + n + m, rec + rec_out, f.col_s.begin());
+      family_return(w, c, PC, c.time_limit_reached, t1 - c.t0, t_lin - c.t_lin0, cone_iter_ms * std::max(c.iter, 1), &sols[c.prob],
+                    &infos[c.prob]);
+      returned[c.prob] = 1;
+      c.prob = -1;
+      --busy;
+    }
+  };
+
+  fill(0, true);
+  real *part = f.part.p, *nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, *warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
+  bool sigint = false;
+  int i = 0, last = -1;
+  for (;; ++i) {
+    { // a loaded slot becomes a running column at the top of its start iteration: one wait, one control record
+      bool due = false;
+      for (int k = 0; k < K; ++k) due = due || (cols[k].pending && cols[k].start == i);
+      if (due) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int k = 0; k < K; ++k) {
+          FamCol &c = cols[k];
+          if (!c.pending || c.start != i) continue;
+          c.pending = c.frozen = false;
+          c.t0 = now_ms();
+          c.t_lin0 = t_lin;
+          w->cone.reset_multi_box_start(k); // the slot projected scratch while it waited
+          ++running;
+        }
+        family_upload_ctl(w, W, K, cols);
+      }
+    }
+    if (running == 0) {
+      if (busy == 0) break; // the queue is empty and every slot is free
+      int s = 2147483647;
+      for (int k = 0; k < K; ++k)
+        if (cols[k].pending) s = std::min(s, cols[k].start);
+      i = s - 1; // nothing runs until then
+      continue;
+    }
+    last = i;
+    cnt[1] += running;
+    int first_mask = 0, norm_mask = 0; // per column what the chunk loop derives from i: here from j = i - start
+    for (int k = 0; k < K; ++k) {
+      if (cols[k].frozen) continue;
+      if (i - cols[k].start < FEASIBLE_ITERS) first_mask |= 1 << k;
+      else norm_mask |= 1 << k;
+    }
+    if (norm_mask) FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
+    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
+                                       f.warm.p, n, l, nrm_part, gl, warm_part, norm_mask, f.ctl.p));
+    {
+      const double tl = now_ms();
+      MultiRhs a;
+      a.bx = f.u_t.p;
+      a.by = f.u_t.p + nw;
+      a.s = f.warm.p;
+      a.pre_stopped = frozen;
+      if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
+      for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = 0, wsc[k] = 1;
+      if (w->cg_tol_override > 0) {
+        for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
+      } else {
+        for (int k = 0; k < K; ++k) {
+          if (cols[k].frozen) continue;
+          tolv[k] = std::min(cols[k].r_n.nm_ax_s_btau, cols[k].r_n.nm_px_aty_ctau);
+          wsc[k] = (real)1.0 / std::pow((real)(i - cols[k].start) + 1, (real)CG_RATE);
+        }
+        a.warm_part = warm_part;
+        a.warm_cnt = gl;
+        a.warm_scale_col = wsc;
+      }
+      w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
+      t_lin += now_ms() - tl;
+    }
+    if (norm_mask)
+      FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
+                                         n + m, part, PSTRIDE, f.ctl.p));
+    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
+                                       f.cw.p, n, l, part, gnm, PSTRIDE, first_mask, f.ctl.p));
+    int cslot = -1;
+    if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
+    if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true);
+    else w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
+    w->cone_timer.stop(cslot, st);
+    w->cone_projs++;
+    const bool check = i % CONVERGED_INTERVAL == 0; // every start is a multiple of CONVERGED_INTERVAL: all columns check together
+    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
+                                       f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
+    unsigned ended = 0;
+    if (check) {
+      if (interrupted()) {
+        sigint = true;
+        break;
+      }
+      family_residuals(w, W, K, cols, i);
+      ++cnt[4];
+      bool changed = false, rescaled = false;
+      const double tnow = now_ms();
+      for (int k = 0; k < K; ++k) {
+        FamCol &c = cols[k];
+        if (c.frozen) continue;
+        c.status = has_converged(c.r_o, w->stgs, c.nm_b_orig, c.nm_c_orig);
+        if (c.status == 0 && w->stgs.time_limit_secs && tnow - c.t0 > 1000. * w->stgs.time_limit_secs) c.time_limit_reached = 1;
+        if (c.status != 0 || c.time_limit_reached) { // as the chunk loop's break: the iteration is not counted, v is not updated
+          c.frozen = changed = true;
+          c.iter = i - c.start;
+          ended |= 1u << k;
+          --running;
+          continue;
+        }
+        real new_scale;
+        if (PC && w->stgs.adaptive_scale &&
+            scale_update_due(c.r_o, c.nm_b_orig, c.nm_c_orig, c.scale, i - c.start, c.sum_log_scale_factor, c.n_log_scale_factor,
+                             c.last_scale_update_iter, &new_scale)) {
+          c.scale_updates++;
+          c.scale = new_scale;
+          c.upd = rescaled = true;
+        }
+      }
+      if (changed || rescaled) family_upload_ctl(w, W, K, cols); // the stream has been waited on and nothing has been enqueued since
+      if (rescaled) {
+        apply_scales();
+        update_g(f.ctl.p->keep);
+        FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
+        for (int k = 0; k < K; ++k) cols[k].upd = false;
+      }
+      if (running > 0)
+        FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
+                                           f.ctl.p));
+    }
+    unsigned capped = 0; // the column's last iteration: its residuals as they stand after it, as the chunk loop's after its last
+    for (int k = 0; k < K; ++k)
+      if (!cols[k].frozen && i - cols[k].start + 1 == max_iters) capped |= 1u << k;
+    if (capped) {
+      family_residuals(w, W, K, cols, i + 1, capped);
+      ++cnt[4];
+      for (int k = 0; k < K; ++k)
+        if ((capped >> k) & 1u) {
+          cols[k].frozen = true;
+          cols[k].iter = max_iters;
+          --running;
+        }
+      family_upload_ctl(w, W, K, cols);
+      ended |= capped;
+    }
+    if (ended) {
+      take_out(ended);
+      fill((i / CONVERGED_INTERVAL + 1) * CONVERGED_INTERVAL, false);
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  HIP_CHECK(hipGetLastError());
+  w->cone_timer.harvest();
+  cnt[0] = last + 1;
+  cnt[2] = cnt[0] * W - cnt[1];
+  return sigint;
+}
+
+static scs_int family_stream_solve(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc, scs_int own_scale,
+                                   const scs_float *scales, scs_int width, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  const char *name = "scs_amd_solve_family_stream";
+  if (!w || !B || !Cc || !sols || !infos || nprob < 1) {
+    printf("ERROR: %s: missing ScsWork, B, Cc, ScsSolution or ScsInfo input, or nprob < 1\n", name);
+    return SCS_FAILED;
+  }
+  if (width != 0 && width != 2 && width != 4 && width != 8 && width != 16) { // before the workspace is looked at
+    printf("ERROR: %s: width must be 0 (chosen from nprob), 2, 4, 8 or 16\n", name);
+    return SCS_FAILED;
+  }
+  w->stream_arg_refusal = nullptr;
+  auto refuse = [&](const char *why) {
+    w->stream_arg_refusal = why;
+    printf("ERROR: %s\n", why);
+    return (scs_int)SCS_FAILED;
+  };
+  if ((long long)ldb < (long long)w->m || (long long)ldc < (long long)w->n) return refuse("scs_amd_solve_family_stream: ldb < m or ldc < n");
+  if (const char *why = family_stream_refusal(w, own_scale != 0)) {
+    printf("ERROR: %s\n", why);
+    return SCS_FAILED;
+  }
+  if (!own_scale && scales)
+    return refuse("scs_amd_solve_family_stream: scales must be NULL with own_scale == 0: the problems then share the workspace's scale");
+  if (scales)
+    for (scs_int k = 0; k < nprob; ++k)
+      if (!std::isfinite((double)scales[k]) || !(scales[k] > 0))
+        return refuse("scs_amd_solve_family_stream: every one of the scales must be a positive finite number");
+  if (w->stale) { // the last scs_amd_update_matrix failed half way
+    for (scs_int k = 0; k < nprob; ++k)
+      fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
+    return SCS_FAILED;
+  }
+  if ((long long)nprob > 2147483647LL) return refuse("scs_amd_solve_family_stream: nprob exceeds 2^31 - 1");
+  const int W = width ? (int)width : std::max(2, multi_width(std::min<scs_int>(nprob, MULTI_W_MAX)));
+  InterruptListener listener;
+  std::vector<char> returned((size_t)nprob, 0);
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    if (w->stgs.verbose) print_header(w);
+    const bool sigint = own_scale ? family_stream_run<true>(w, (int)nprob, W, B, (size_t)ldb, Cc, (size_t)ldc, scales, sols, infos, warm_start, returned)
+                                  : family_stream_run<false>(w, (int)nprob, W, B, (size_t)ldb, Cc, (size_t)ldc, nullptr, sols, infos, warm_start, returned);
+    if (sigint) {
+      (void)hipStreamSynchronize(w->stream);
+      for (scs_int k = 0; k < nprob; ++k)
+        if (!returned[k]) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_SIGINT, "interrupted", "interrupted");
+    }
+    if (w->stgs.verbose) print_rule();
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
+    const std::string msg = std::string("HIP error in ") + name;
+    for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, msg.c_str(), "failure");
+    return SCS_FAILED;
+  }
+  return 0;
+}
+
 extern "C" {
+
+const char *scs_amd_solve_family_stream_refusal(const ScsWork *w, scs_int own_scale) {
+  if (!w) return nullptr;
+  if (const char *why = family_stream_refusal(w, own_scale != 0)) return why;
+  return w->stream_arg_refusal; // the arguments the last call was refused for, until a call is accepted
+}
+
+scs_int scs_amd_solve_family_stream(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    scs_int own_scale, const scs_float *scales, scs_int width, ScsSolution *sols, ScsInfo *infos,
+                                    scs_int warm_start) {
+  return family_stream_solve(w, nprob, B, ldb, Cc, ldc, own_scale, scales, width, sols, infos, warm_start);
+}
+
+void scs_amd_family_stream_get_counters(const ScsWork *w, long long out[6]) {
+  for (int q = 0; q < 6; ++q) out[q] = w && w->fam ? w->fam->counters[q] : 0;
+}
 
 const char *scs_amd_solve_family_refusal(const ScsWork *w) { return w ? family_refusal(w) : nullptr; }
 

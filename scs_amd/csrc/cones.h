@@ -89,6 +89,7 @@ struct ConeDev {
   // keeps a column-major copy of the box rows of the m x W block Ry; to be called again when Ry changes
   void set_multi_ry(const real *Ry, int W);
   void reset_multi_cold();                                       // box Newton starts and eigenbases of the block state: cold
+  void reset_multi_box_start(int k);                             // the per-column half of it: column position k's box Newton start
   // launches shared by the two paths
   void launch_box(real *tx, real *t_warm, const real *rb);
   void launch_psd_lds(real *cw, int nblocks, const int *off, const int *kk, real *tscratch, real *vprev, int warm);

@@ -350,6 +350,15 @@ void ConeDev::reset_multi_cold() {
   for (BigPsd *b : mc.big) b->reset_warm_start();
 }
 
+// Column position k alone starts its box Newton iteration at 1 again (cones.c:1560): a position that takes another problem while
+// its neighbours run on (scs_amd_solve_family_stream).  The other cones carried here keep nothing between projections except the
+// PSD eigenbases, whose cold-restart counter belongs to the width: a caller with PSD blocks uses reset_multi_cold.
+void ConeDev::reset_multi_box_start(int k) {
+  if (!multi || bsize <= 0 || k < 0 || k >= multi->width) return;
+  static const real one = 1; // static: the copy may run after this returns
+  HIP_CHECK(hipMemcpyAsync(multi->box_t.p + k, &one, sizeof(real), hipMemcpyHostToDevice, stream));
+}
+
 // Ry (device, m x W block: every column its own r_y) -> the column-major copy of its box rows that launch_box takes a column of.
 // The copy lives with the block state of width W: a change of width (ensure_multi) drops it.
 void ConeDev::set_multi_ry(const real *Ry, int W) {

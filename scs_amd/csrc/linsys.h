@@ -87,6 +87,9 @@ struct MultiRhs {
   const real *warm_part = nullptr;
   int warm_cnt = 0;
   real warm_scale = 0;
+  // non-null: W host values, column k takes warm_scale_col[k] where the others take warm_scale (columns that stand at different
+  // iterations of their own solves: scs_amd_solve_family_stream); passed to the kernel by value, not read after the call returns
+  const real *warm_scale_col = nullptr;
   const int *pre_stopped = nullptr;
   // every column under its own diag_r: R_x (n x W), R_y (m x W) and the preconditioner built from them by precond_multi_blocks
   // (n x W); padding columns hold ordinary finite values (1).  All three or none; all null = the workspace's shared rx / ry / M.

@@ -104,10 +104,14 @@ __device__ __forceinline__ void set_all_done(CgCtlM *ctl, int W, bool col_done) 
 // solve_dev forms it (src/scs.c:745-762), tol.t[k] being the cap.  `pre` (W ints, or null): columns that are stopped on entry --
 // nothing of theirs is read or written, here or by any later kernel of the solve, and they count no iteration.
 // PERCOL: ry is an m x W block (every column its own R_y) instead of one vector of m.
-template <int W, bool PERCOL = false>
+// WS: the type of warm_scale -- `real`, one factor for the block, or TolArgs, column k its own factor warm_scale.t[k]
+// (MultiRhs::warm_scale_col), in the same expression: equal factors give the scalar form's bits.
+__device__ __forceinline__ real warm_scale_of(real s, int) { return s; }
+__device__ __forceinline__ real warm_scale_of(const TolArgs &s, int col) { return s.t[col]; }
+template <int W, bool PERCOL = false, typename WS = real>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by, const real *__restrict__ ry, real *tmp, int n, int m,
                                                              const real *part, int pcount, CgCtlM *ctl, TolArgs tol, int K, int max_its,
-                                                             const real *warm_part, int warm_cnt, real warm_scale, const int *pre) {
+                                                             const real *warm_part, int warm_cnt, WS warm_scale, const int *pre) {
   __shared__ real red[4 * W];
   const real nb = reduce_partials_col_max<W>(part, pcount, red);
   const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (size_t)gridDim.x * blockDim.x;
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_rhs_prep(real *bx, real *by,
   const bool zero = stopped || col >= K || nb <= (real)1e-12;
   real t = col < K ? tol.t[col] : (real)0;
   if (warm_part) {
-    const real nw = reduce_partials_col_max<W>(warm_part, warm_cnt, red) * warm_scale;
+    const real nw = reduce_partials_col_max<W>(warm_part, warm_cnt, red) * warm_scale_of(warm_scale, col);
     t = t < nw ? t : nw;
     t = (real)0.2 * t;                     // CG_TOL_FACTOR, include/glbopts.h:250
     t = t > (real)1e-12 ? t : (real)1e-12; // CG_BEST_TOL, glbopts.h:247
@@ -406,7 +410,16 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
   const long long mv0 = n_matvecs;
 
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_absmax<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, nx, by, ny, mw.part_max.p));
-  if (percol)
+  if (a.warm_scale_col) { // every column its own factor of the warm-start term
+    TolArgs ws{};
+    for (int k = 0; k < W; ++k) ws.t[k] = a.warm_scale_col[k];
+    if (percol)
+      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, true, TolArgs>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, a.ry, tmpb, n,
+                                           m, mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, ws, a.pre_stopped));
+    else
+      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, false, TolArgs>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, ry.p, tmpb, n,
+                                           m, mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, ws, a.pre_stopped));
+  } else if (percol)
     MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, true>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, a.ry, tmpb, n, m,
                                          mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
   else

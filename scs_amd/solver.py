@@ -105,7 +105,7 @@ class SCS:
                                                px.ctypes.data_as(T.fp) if px is not None else None) != 0:
                 raise RuntimeError("scs_amd_update_matrix failed")
 
-    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None, scale=None, own_scale=False):
+    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None, scale=None, own_scale=False, stream=False, width=None):
         """scs_amd_solve_family: K problems that share A, P and the cones of this object and differ in (b, c), in one
         device-resident loop.  B: m x K, C: n x K, as arrays or as lists of K vectors.  With warm_start, x (n x K), y and
         s (m x K) seed the columns.  Returns a list of K dicts in the shape `solve` returns.  The object's own problem and
@@ -113,7 +113,11 @@ class SCS:
         otherwise ValueError with the library's message.
         own_scale=True (scs_amd_solve_family_scaled): every problem runs under its own scale and the object's adaptive_scale is
         honoured, problem by problem; info["scale"] and info["scale_updates"] are the problem's own.  scale: K initial scales
-        (implies own_scale); without it every problem starts at the object's scale."""
+        (implies own_scale); without it every problem starts at the object's scale.
+        stream=True (scs_amd_solve_family_stream): the K problems are a queue through one block of `width` columns (2, 4, 8 or
+        16; None: chosen from K), a finished column's slot going to the next problem, instead of chunks of 16 that each wait
+        for their slowest column; every problem has the bits the call without stream gives it at that width.  Cones with PSD
+        blocks are refused (ValueError with the library's message); a width that is none of those raises ValueError."""
         if not self._w:
             raise RuntimeError("solver was closed")
         m, n = self._prob.m, self._prob.n
@@ -132,13 +136,21 @@ class SCS:
         if K < 1 or C_.shape[1] != K:
             raise ValueError("B and C must have the same number K >= 1 of columns")
         scaled = bool(own_scale) or scale is not None
+        if width is not None and not stream:
+            raise ValueError("width belongs to stream=True")
+        if stream:
+            if width is not None and (isinstance(width, bool) or not isinstance(width, (int, np.integer))
+                                      or int(width) not in capi.STREAM_WIDTHS[1:]):
+                raise ValueError("width must be None, 2, 4, 8 or 16")
+            width = 0 if width is None else int(width)
         if scale is not None:
             scale = np.asarray(scale, dtype=float).reshape(-1)
             if scale.shape[0] != K:
                 raise ValueError("scale must hold one initial scale per problem")
-        why = (self._lib.scs_amd_solve_family_scaled_refusal if scaled else self._lib.scs_amd_solve_family_refusal)(self._w)
-        if why:
-            raise ValueError(why.decode())
+        if not stream:
+            why = (self._lib.scs_amd_solve_family_scaled_refusal if scaled else self._lib.scs_amd_solve_family_refusal)(self._w)
+            if why:
+                raise ValueError(why.decode())
         warm = None
         if warm_start:
             if x is None or y is None or s is None:
@@ -146,12 +158,22 @@ class SCS:
             warm = (block(x, n, "x"), block(y, m, "y"), block(s, m, "s"))
             if any(v.shape[1] != K for v in warm):
                 raise ValueError("warm-start blocks must have K columns")
-        if scaled:
+        if stream:
+            rc, out = capi.solve_family_stream(self._lib, self._w, B, C_, width=int(width), own_scale=scaled, scales=scale, warm=warm)
+        elif scaled:
             rc, out = capi.solve_family_scaled(self._lib, self._w, B, C_, scales=scale, warm=warm)
         else:
             rc, out = capi.solve_family(self._lib, self._w, B, C_, warm=warm)
+        if rc != 0 and stream:
+            # The stream entry's refusal function also reports the arguments the LAST call was refused for (a scale that is not
+            # positive, say), until a call is accepted: asked before the call it would hold a refusal that no longer applies, so
+            # it is asked after a call that failed, where it speaks of that call.  The library refuses before any device work.
+            why = self._lib.scs_amd_solve_family_stream_refusal(self._w, 1 if scaled else 0)
+            if why:
+                raise ValueError(why.decode())
         if rc != 0:
-            raise RuntimeError("scs_amd_solve_family_scaled failed" if scaled else "scs_amd_solve_family failed")
+            raise RuntimeError("scs_amd_solve_family_stream failed" if stream else
+                               "scs_amd_solve_family_scaled failed" if scaled else "scs_amd_solve_family failed")
         return out
 
     def close(self):
