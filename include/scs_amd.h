@@ -408,6 +408,41 @@ scs_int scs_amd_solve_lin_sys_multi_r(ScsLinSysWork *w, scs_int nrhs, const scs_
  * are read as ordinary columns (the caller fills padding columns, e.g. with 1).  -1 for nrhs outside 1 .. 16 (1 runs at W = 2). */
 scs_int scs_amd_linsys_mat_vec_multi_r_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *R_dev,
                                            const scs_float *X_dev, scs_float *Y_dev);
+/* ---- every column of a block with its own values of A and P ----
+ * The blocks above read one A and one P for all columns.  Here the K systems share the PATTERN given to scs_init_lin_sys_work and
+ * nothing else: column k has its own values of A and P (and its own diag_r), and computes what
+ *     scs_amd_linsys_update_values(w, AX[:, k], PX[:, k]); scs_update_lin_sys_diag_r(w, DR[:, k]);
+ *     scs_solve_lin_sys(w, B[:, k], S[:, k], tol[k])
+ * computes (private.c:50-82, :106-119, :133-217, :284-327) -- time-varying dynamics, scenario-dependent coefficients, a sweep over
+ * a coefficient as one block.  The row pointers and indices are read once per product for all columns; the values are stored as
+ * blocks of nnz x W in the block layout, so the W lanes that gather W contiguous values of the vector also read W contiguous
+ * values of the matrix.  Bit for bit, column k is column k of scs_amd_solve_lin_sys_multi_r at the same nrhs on a workspace
+ * brought to values k by scs_amd_linsys_update_values; with every column holding the workspace's own values the call returns the
+ * bits and iteration counts of scs_amd_solve_lin_sys_multi_r (DR given) or scs_amd_solve_lin_sys_multi (DR NULL).  Independence,
+ * frozen columns, determinism and the statistics as above.
+ * Memory: (2 nnz(A) + nnz(full P) + n) W values and one staged column, allocated by the FIRST set call only (with the R blocks of
+ * scs_amd_solve_lin_sys_multi_r and the position maps of scs_amd_linsys_update_values), rebuilt when a set call needs a wider
+ * block, released by scs_amd_linsys_free_values_multi or scs_free_lin_sys_work; an allocation failure leaves the workspace usable
+ * without value blocks.  The workspace's own values, layouts, diag_r, preconditioner, captured graph and single-vector state are
+ * neither read for the columns nor written: scs_solve_lin_sys, _multi and _multi_r return the bits they returned before, and
+ * scs_amd_linsys_update_values / scs_update_lin_sys_diag_r on the same workspace neither read nor change the stored blocks.
+ * Refusals, all before any device call, message on stderr, -1, the workspace, the stored blocks and B untouched: w / AX / B / tol
+ * NULL; PX given without P or missing with P; nrhs < 1 or > 16 (no chunking: set and solve in groups); a short leading
+ * dimension; a non-finite value in AX or PX; a non-finite or non-positive value in DR; a row-sharded workspace; a solve or a
+ * product before a set call or with another nrhs than the set call's.  -1 on a HIP failure with the stream drained. */
+/* stores the values of nrhs (1..16) systems on the pattern given to scs_init_lin_sys_work: AX column-major nnz(A) x nrhs in the CSC
+ * order of init's A, PX nnz(upper P) x nrhs (NULL iff the workspace has no P); host arrays, not modified.  Replaces the values of
+ * an earlier set call.  Returns with the stream idle (the arrays may be pageable and reused). */
+scs_int scs_amd_linsys_set_values_multi(ScsLinSysWork *w, scs_int nrhs, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx);
+/* column k: scs_amd_linsys_update_values(AX[:,k], PX[:,k]); scs_update_lin_sys_diag_r(DR[:,k]); scs_solve_lin_sys(B[:,k], S[:,k], tol[k]).
+ * DR may be NULL (the workspace's diag_r in every column); the rest as scs_amd_solve_lin_sys_multi_r; nrhs must equal the set call's.
+ * ONE column runs as a block of width 2. */
+scs_int scs_amd_solve_lin_sys_multi_v(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
+                                      const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters);
+/* Y(:,k) = (R_x,k + P_k + A_k' R_y,k^-1 A_k) X(:,k) on device blocks, as scs_amd_linsys_mat_vec_multi_r_dev (R_dev NULL: the
+ * workspace's diag_r in every column) */
+scs_int scs_amd_linsys_mat_vec_multi_v_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *R_dev, const scs_float *X_dev, scs_float *Y_dev);
+void scs_amd_linsys_free_values_multi(ScsLinSysWork *w);   /* releases the value blocks; NULL-safe */
 /* the SpMV kernel these entries (and scs_solve_lin_sys) run for A (which = 0) / A' (which = 1): the strings of
  * scs_amd_get_spmv_kernel_name.  Returns the length needed. */
 scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap);

@@ -176,6 +176,15 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
         lib.scs_amd_solve_lin_sys_multi_r.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, fp, scs_int, fp, T.ip]
         lib.scs_amd_linsys_mat_vec_multi_r_dev.restype = scs_int
         lib.scs_amd_linsys_mat_vec_multi_r_dev.argtypes = [C.c_void_p, scs_int, C.c_void_p, C.c_void_p, C.c_void_p]  # device pointers
+        # every column of a block with its own values of A and P
+        lib.scs_amd_linsys_set_values_multi.restype = scs_int
+        lib.scs_amd_linsys_set_values_multi.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int]
+        lib.scs_amd_solve_lin_sys_multi_v.restype = scs_int
+        lib.scs_amd_solve_lin_sys_multi_v.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, fp, scs_int, fp, T.ip]
+        lib.scs_amd_linsys_mat_vec_multi_v_dev.restype = scs_int
+        lib.scs_amd_linsys_mat_vec_multi_v_dev.argtypes = [C.c_void_p, scs_int, C.c_void_p, C.c_void_p, C.c_void_p]  # device pointers
+        lib.scs_amd_linsys_free_values_multi.restype = None
+        lib.scs_amd_linsys_free_values_multi.argtypes = [C.c_void_p]
         lib.scs_amd_linsys_sync.restype = scs_int
         lib.scs_amd_linsys_sync.argtypes = [C.c_void_p]
         lib.scs_amd_linsys_spmv_kernel_name.restype = scs_int

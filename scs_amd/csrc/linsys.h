@@ -62,6 +62,14 @@ struct MultiWork {
   // Allocated at the first per-column call only (ensure_multi_r): a caller who never makes one allocates what is listed above.
   int rwidth = 0;           // width these three were allocated for (0: not allocated)
   DevBuf<real> rxb, ryb, Mb; // n W, m W, n W
+  // per-column values (scs_amd_linsys_set_values_multi): the values of every column's A and P on the workspace's pattern, blocks of
+  // nnz x W' in the block layout at the layout width W' of the last set call's `vcols` columns (W' <= vwidth); padding columns 0.
+  // Allocated by the first set call only, rebuilt when a set call needs a wider block (ensure_multi_values).
+  int vwidth = 0;           // width the value blocks were allocated for (0: not allocated)
+  int vcols = 0;            // columns of the set call in force (0: none)
+  DevBuf<real> vA, vAt;     // nnz(A) vwidth each: CSR(A) order, CSC order
+  DevBuf<real> vP, vPdiag;  // nnz(full P) vwidth, n vwidth; only with P
+  DevBuf<real> vstage;      // one column of the caller's values on its way into the blocks: max(nnz(A), nnz(upper P))
 };
 
 // ONE linear system split by rows of A over several devices (the operator split is
@@ -94,6 +102,10 @@ struct MultiRhs {
   // every column under its own diag_r: R_x (n x W), R_y (m x W) and the preconditioner built from them by precond_multi_blocks
   // (n x W); padding columns hold ordinary finite values (1).  All three or none; all null = the workspace's shared rx / ry / M.
   const real *rx = nullptr, *ry = nullptr, *Minv = nullptr;
+  // every column its own values of A (CSR order), A' (CSC order) and the symmetric P, value blocks of nnz x W (MultiWork::vA ...);
+  // vP and vPdiag with P only; needs rx / ry / Minv (Minv built by precond_multi_blocks from vAt and vPdiag).  All null = the
+  // workspace's shared values.
+  const real *vA = nullptr, *vAt = nullptr, *vP = nullptr, *vPdiag = nullptr;
 };
 
 struct LinSys {
@@ -190,12 +202,18 @@ struct LinSys {
   void ensure_multi(int W);
   void ensure_multi_r(int W); // ensure_multi plus the three R blocks of MultiWork
   // dcol: e.d is a block (rows x W), one divisor / multiplier per column (EPI_DIV, EPI_GP, EPI_NEGDIV)
+  // vals: the matrix's values per column, an nnz x W block in mat's entry order (null: mat's own, shared by the columns)
   void launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
-                   bool dcol = false);
-  // rxb / ryb (both or neither): R_x / R_y per column as blocks instead of the workspace's own
+                   bool dcol = false, const real *vals = nullptr);
+  // rxb / ryb (both or neither): R_x / R_y per column as blocks instead of the workspace's own; vA / vAt / vP: value blocks
   void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr,
-                         const real *rxb = nullptr, const real *ryb = nullptr);
-  void precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv);
+                         const real *rxb = nullptr, const real *ryb = nullptr, const real *vA = nullptr, const real *vAt = nullptr,
+                         const real *vP = nullptr);
+  void precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv, const real *vAt = nullptr, const real *vPdiag = nullptr);
+  // value blocks of the per-value solves (MultiWork::vA ...; scs_amd_linsys_set_values_multi)
+  void ensure_multi_values(int W);
+  void set_multi_values(int K, int W, const real *AX, size_t ldax, const real *PX, size_t ldpx);
+  void free_multi_values();
   void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
   void solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out);
   // ---- new values on the pattern given to init (scs_amd_linsys_update_values, include/scs_amd.h) ----

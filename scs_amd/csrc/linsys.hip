@@ -1929,6 +1929,123 @@ scs_int scs_amd_solve_lin_sys_multi_r(ScsLinSysWork *w, scs_int nrhs, const scs_
   return solve_multi_host(w, nrhs, DR, lddr, B, ldb, S, lds, tol, iters);
 }
 
+// ---- K systems on the workspace's pattern, every column its own values of A and P (include/scs_amd.h) ----
+static bool all_finite(const scs_float *v, long long len);
+static scs_int refuse(const char *what) {
+  fprintf(stderr, "scs_amd: %s\n", what);
+  return -1;
+}
+// layout width of a per-value block of nrhs columns: one column runs at width 2, off the single-vector state
+static int values_width(scs_int nrhs) { return nrhs == 1 ? 2 : multi_width((long long)nrhs); }
+
+// the checks come before any device call; a refused call leaves the stored blocks as they were
+scs_int scs_amd_linsys_set_values_multi(ScsLinSysWork *w, scs_int nrhs, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+  if (!w || !AX) return refuse("set_values_multi: w and AX must be given");
+  LinSys &ls = w->ls;
+  if (ls.shard) return refuse("set_values_multi: a row-sharded workspace takes no values per column");
+  if ((PX != nullptr) != ls.has_P) return refuse("set_values_multi: PX must be given exactly when the workspace has a P");
+  if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("set_values_multi: nrhs must be 1 .. 16 (set and solve in groups)");
+  const long long nza = ls.At.nnz, nzp = ls.has_P ? ls.nnzP_up : 0;
+  if ((long long)ldax < nza || (PX && (long long)ldpx < nzp)) return refuse("set_values_multi: a leading dimension is shorter than its column");
+  for (scs_int k = 0; k < nrhs; ++k)
+    if (!all_finite(AX + (size_t)k * (size_t)ldax, nza) || (PX && !all_finite(PX + (size_t)k * (size_t)ldpx, nzp)))
+      return refuse("set_values_multi: a matrix value is not finite");
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    ls.set_multi_values((int)nrhs, values_width(nrhs), AX, (size_t)ldax, PX, (size_t)ldpx);
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(ls.stream);
+    return -1;
+  }
+  return 0;
+}
+
+void scs_amd_linsys_free_values_multi(ScsLinSysWork *w) {
+  if (!w) return;
+  (void)hipSetDevice(w->device);
+  (void)hipStreamSynchronize(w->ls.stream);
+  w->ls.free_multi_values();
+}
+
+// the workspace's diag_r in every column of its R blocks at width W (a per-value call without an R of its own)
+static void workspace_r_into_blocks(LinSys &ls, int W) {
+  MultiWork &mw = *ls.multi;
+  const size_t n = ls.n, m = ls.m;
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_replicate<MW>, dim3(ls.vec_grid((long long)n * W)), dim3(SCSAMD_BLOCK), 0, ls.stream,
+                                       (const real *)ls.rx.p, mw.rxb.p, n));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_replicate<MW>, dim3(ls.vec_grid((long long)m * W)), dim3(SCSAMD_BLOCK), 0, ls.stream,
+                                       (const real *)ls.ry.p, mw.ryb.p, m));
+}
+
+scs_int scs_amd_solve_lin_sys_multi_v(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
+                                      const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
+  if (!w || !B || !tol) return refuse("solve_lin_sys_multi_v: w, B and tol must be given");
+  LinSys &ls = w->ls;
+  if (ls.shard) return refuse("solve_lin_sys_multi_v: not available on a row-sharded workspace");
+  if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("solve_lin_sys_multi_v: nrhs must be 1 .. 16 (set and solve in groups)");
+  if (!ls.multi || ls.multi->vcols == 0) return refuse("solve_lin_sys_multi_v: no values are set (scs_amd_linsys_set_values_multi)");
+  if (ls.multi->vcols != (int)nrhs) return refuse("solve_lin_sys_multi_v: nrhs differs from the set call's");
+  const size_t n = ls.n, m = ls.m, sz = sizeof(real);
+  const long long len = (long long)(n + m);
+  if ((long long)ldb < len || (S && (long long)lds < (long long)n) || (DR && (long long)lddr < len))
+    return refuse("solve_lin_sys_multi_v: a leading dimension is shorter than its column");
+  if (DR)
+    for (scs_int k = 0; k < nrhs; ++k) {
+      const scs_float *d = DR + (size_t)k * (size_t)lddr;
+      for (long long i = 0; i < len; ++i)
+        if (!(std::isfinite((double)d[i]) && d[i] > 0)) return refuse("solve_lin_sys_multi_v: diag_r must be finite and positive");
+    }
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    const int K = (int)nrhs, W = values_width(nrhs);
+    ls.ensure_multi_r(W);
+    MultiWork &mw = *ls.multi;
+    const int g = ls.vec_grid(len);
+    if (DR) { // staged column-major in gt (B comes after it, in stream order); padding columns 1
+      HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, DR, (size_t)lddr * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.rxb.p, (int)n, mw.ryb.p,
+                                           (int)m, K, (real)1));
+    } else {
+      workspace_r_into_blocks(ls, W);
+    }
+    ls.precond_multi_blocks(W, mw.rxb.p, mw.ryb.p, mw.Mb.p, mw.vAt.p, mw.vPdiag.p); // every column's, from its own values
+    if (S) { // staged column-major in z, transposed into s on the device
+      HIP_CHECK(hipMemcpy2DAsync(mw.z.p, n * sz, S, (size_t)lds * sz, n * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.z.p, mw.s.p, (int)n,
+                                           (real *)nullptr, 0, K, (real)0));
+    }
+    HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, B, (size_t)ldb * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
+                                         (int)m, K, (real)0));
+    MultiRhs a;
+    a.bx = mw.bx.p;
+    a.by = mw.by.p;
+    a.s = S ? mw.s.p : nullptr;
+    a.rx = mw.rxb.p;
+    a.ry = mw.ryb.p;
+    a.Minv = mw.Mb.p;
+    a.vA = mw.vA.p;
+    a.vAt = mw.vAt.p;
+    a.vP = ls.has_P ? mw.vP.p : nullptr;
+    a.vPdiag = ls.has_P ? mw.vPdiag.p : nullptr;
+    int its[MULTI_W_MAX];
+    ls.solve_multi_blocks(K, W, a, tol, its);
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
+                                         (int)m, K));
+    HIP_CHECK(hipMemcpy2DAsync(B, (size_t)ldb * sz, mw.gt.p, (n + m) * sz, (n + m) * sz, (size_t)K, hipMemcpyDeviceToHost, ls.stream));
+    HIP_CHECK(hipStreamSynchronize(ls.stream));
+    HIP_CHECK(hipGetLastError());
+    if (iters)
+      for (int k = 0; k < K; ++k) iters[k] = its[k];
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(ls.stream); // nothing of this call may still be reading or writing the caller's block
+    return -1;
+  }
+  return 0;
+}
+
 scs_int scs_update_lin_sys_diag_r(ScsLinSysWork *w, const scs_float *new_diag_r) {
   if (!w || !new_diag_r) return -1;
   try {
@@ -2036,6 +2153,35 @@ scs_int scs_amd_linsys_mat_vec_multi_r_dev(ScsLinSysWork *w, scs_int nrhs, const
     ls.ensure_multi(W);
     const real *R = static_cast<const real *>(R_dev);
     ls.mat_vec_multi_dev(W, static_cast<const real *>(X_dev), static_cast<real *>(Y_dev), nullptr, nullptr, nullptr, R, R + (size_t)ls.n * W);
+    HIP_CHECK(hipGetLastError());
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    return -1;
+  }
+  return 0;
+}
+// G_k X(:,k) with the values of the last set call and R_x / R_y per column (R_dev as above; null: the workspace's diag_r in every
+// column, replicated into the workspace's R blocks)
+scs_int scs_amd_linsys_mat_vec_multi_v_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *R_dev, const scs_float *X_dev, scs_float *Y_dev) {
+  if (!w || !X_dev || !Y_dev) return refuse("mat_vec_multi_v_dev: w, X_dev and Y_dev must be given");
+  LinSys &ls = w->ls;
+  if (ls.shard) return refuse("mat_vec_multi_v_dev: not available on a row-sharded workspace");
+  if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("mat_vec_multi_v_dev: nrhs must be 1 .. 16");
+  if (!ls.multi || ls.multi->vcols == 0) return refuse("mat_vec_multi_v_dev: no values are set (scs_amd_linsys_set_values_multi)");
+  if (ls.multi->vcols != (int)nrhs) return refuse("mat_vec_multi_v_dev: nrhs differs from the set call's");
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    const int W = values_width(nrhs);
+    ls.ensure_multi_r(W);
+    MultiWork &mw = *ls.multi;
+    const real *rxb = static_cast<const real *>(R_dev), *ryb = rxb ? rxb + (size_t)ls.n * W : nullptr;
+    if (!rxb) {
+      workspace_r_into_blocks(ls, W);
+      rxb = mw.rxb.p;
+      ryb = mw.ryb.p;
+    }
+    ls.mat_vec_multi_dev(W, static_cast<const real *>(X_dev), static_cast<real *>(Y_dev), nullptr, nullptr, nullptr, rxb, ryb, mw.vA.p,
+                         mw.vAt.p, ls.has_P ? mw.vP.p : nullptr);
     HIP_CHECK(hipGetLastError());
   } catch (const std::exception &ex) {
     fprintf(stderr, "%s\n", ex.what());

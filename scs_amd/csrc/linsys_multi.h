@@ -21,6 +21,13 @@
 // csr_block_kernel, PERCOL of k_m_rhs_prep / k_m_cg_init / k_m_cg_update); A and P are still read once per product for all
 // columns.  The workspace's own rx, ry, M, captured graph and single-vector state are neither read nor written.  Three more blocks
 // (2 n W + m W values), allocated at the first per-column call only.
+//
+// Per-column values (MultiRhs::vA / vAt / vP / vPdiag): K systems on one pattern, column k with its own values of A and P, i.e. it
+// computes what scs_amd_linsys_update_values(values k) followed by the per-column-R solve computes.  The values are blocks of
+// nnz x W in the block layout (the VCOL form of csr_block_kernel and k_m_precond, spmm.h); the row pointers and indices are the
+// workspace's and are read once per product for all columns.  Always under per-column R: a caller without an R of their own gets
+// the workspace's replicated into the R blocks.  The workspace's A.val, At.val, P.val, Pdiag, rx, ry, M, layouts, captured graph
+// and single-vector state are neither read for the columns nor written.  Allocated by the first set call only.
 #pragma once
 
 namespace scsamd {
@@ -57,20 +64,52 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_from_block(real *dst, const 
 // lane evaluates k_precond's expression in k_precond's order -- start from rx, the entries in index order, pdiag last, one
 // reciprocal -- so column k holds the bits k_precond gives for diag_r_k.  Rows are summed sequentially per lane, long ones too:
 // the kernel runs once per solve, not once per iteration.
-template <int W>
+// VCOL: every column its own values (ValBlk, spmm.h) -- a lane reads its own value of A', the W lanes of a row W contiguous ones,
+// and pdiag is an n x W block; the expression and its order are the same.
+template <int W, bool VCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_precond(CsrView At, const real *__restrict__ rx, const real *__restrict__ ry,
-                                                            const real *__restrict__ pdiag, real *M) {
+                                                            const real *__restrict__ pdiag, real *M, ValBlk<VCOL> vb) {
   const size_t total = (size_t)At.rows * W;
   for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < total; f += (size_t)gridDim.x * blockDim.x) {
     const int i = (int)(f / W), col = (int)(f & (W - 1));
     real acc = rx[f];
     for (eoff k = At.ptr[i]; k < At.ptr[i + 1]; ++k) {
-      const real a = At.val[k];
+      const real a = blk_val<W>(vb, At.val, k, col);
       acc += a * a / ry[(size_t)At.idx[k] * W + col];
     }
-    if (pdiag) acc += pdiag[i];
+    if (pdiag) acc += pdiag[VCOL ? f : (size_t)i];
     M[f] = (real)1 / acc;
   }
+}
+
+// One column of new values into a value block through a position map: dst[k * W + col] = src[map[k]] (map null: src[k]).  The
+// maps are those of LinSys::ensure_update_maps -- upd_rpos for CSR(A), upd_fsrc for the symmetric P; CSC(A) is CSR(A') and takes
+// the caller's order as it is.  One launch per column: the source is the one column that is staged at a time.
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_upd_gather_block(const real *__restrict__ src, const eoff *__restrict__ map,
+                                                                     real *__restrict__ dst, long long len, int col) {
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < len; k += (long long)gridDim.x * blockDim.x)
+    dst[(size_t)k * W + col] = src[map ? map[k] : (eoff)k];
+}
+
+// k_upd_pdiag on a value block of the symmetric P: pd[j * W + col] = the stored diagonal entries of row j in their stored order,
+// column by column (the lane mapping of k_m_precond)
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_upd_pdiag(CsrView P, ValBlk<true> vb, real *__restrict__ pd) {
+  const size_t total = (size_t)P.rows * W;
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < total; f += (size_t)gridDim.x * blockDim.x) {
+    const int j = (int)(f / W), col = (int)(f & (W - 1));
+    real s = 0;
+    for (eoff k = P.ptr[j]; k < P.ptr[j + 1]; ++k)
+      if (P.idx[k] == j) s += vb.v[(size_t)(k - vb.bias) * W + col];
+    pd[f] = s;
+  }
+}
+
+// the workspace's R_x / R_y in every column of a block (a caller of the per-value solve who brings no R of their own)
+template <int W>
+__global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_replicate(const real *__restrict__ src, real *__restrict__ dst, size_t len) {
+  for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < len * W; f += (size_t)gridDim.x * blockDim.x) dst[f] = src[f / W];
 }
 
 // |[r_x; r_y]|_inf per column (private.c:296)
@@ -282,22 +321,36 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_direction(real *p, const 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 template <int W>
 static void launch_spmm_w(int epi, bool dcol, int g, hipStream_t st, const CsrView &v, const real *X, real *Y, const EpiArgs &e,
-                          const int *cskip, const int *allskip) {
+                          const int *cskip, const int *allskip, const real *vals, eoff bias) {
+  if (vals) { // every column its own values: the five instantiations the per-value solve uses (per-column d where there is a d)
+    const ValBlk<true> vb{vals, bias};
+    if (dcol != (epi == EPI_DIV || epi == EPI_GP || epi == EPI_NEGDIV)) throw HipError("scs_amd: per-column values run under per-column R");
+    switch (epi) {
+    case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN, false, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
+    case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV, true, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
+    case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP, true, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
+    case EPI_ACC: hipLaunchKernelGGL((csr_block_kernel<W, EPI_ACC, false, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
+    case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV, true, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
+    default: throw HipError("scs_amd: bad block-product epilogue");
+    }
+    return;
+  }
+  const ValBlk<false> vs{};
   if (dcol) { // e.d is a block: the per-column instantiations (the epilogues that have a d)
     switch (epi) {
-    case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
-    case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
-    case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+    case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+    case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+    case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
     default: throw HipError("scs_amd: this block-product epilogue has no per-column form");
     }
     return;
   }
   switch (epi) {
-  case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
-  case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
-  case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
-  case EPI_ACC: hipLaunchKernelGGL((csr_block_kernel<W, EPI_ACC>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
-  case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip); break;
+  case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+  case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+  case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+  case EPI_ACC: hipLaunchKernelGGL((csr_block_kernel<W, EPI_ACC>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+  case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
   default: throw HipError("scs_amd: bad block-product epilogue");
   }
 }
@@ -314,10 +367,11 @@ static void launch_spmm_w(int epi, bool dcol, int g, hipStream_t st, const CsrVi
   } while (0)
 
 void LinSys::launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
-                         bool dcol) {
+                         bool dcol, const real *vals) {
   const int g = spmm_grid(mat.rows, W);
-  const CsrView v = mat.view();
-  MULTI_DISPATCH(W, launch_spmm_w<MW>(epi, dcol, g, stream, v, X, Y, e, cskip, allskip));
+  CsrView v = mat.view();
+  if (vals) v.val = nullptr; // the pattern only: the values are the block's
+  MULTI_DISPATCH(W, launch_spmm_w<MW>(epi, dcol, g, stream, v, X, Y, e, cskip, allskip, vals, (eoff)mat.bias));
   n_spmv++;
 }
 
@@ -357,28 +411,112 @@ void LinSys::ensure_multi_r(int W) {
   mw.rwidth = W;
 }
 
-// Minv(n x W) = the Jacobi preconditioner of every column under its own rx (n x W) / ry (m x W): k_precond per column
-void LinSys::precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv) {
-  const CsrView v = At.view();
+// The value blocks of the per-value solves (scs_amd_linsys_set_values_multi): 2 nnz(A) W + nnz(full P) W + n W values and one
+// staged column.  Allocated by the first set call only, rebuilt when a set call needs a wider block, freed with the workspace or
+// by free_multi_values.  A failed allocation leaves the workspace usable with no value blocks (vwidth = 0).
+void LinSys::free_multi_values() {
+  if (!multi) return;
+  MultiWork &mw = *multi;
+  mw.vwidth = 0;
+  mw.vcols = 0;
+  mw.vA.release();
+  mw.vAt.release();
+  mw.vP.release();
+  mw.vPdiag.release();
+  mw.vstage.release();
+}
+void LinSys::ensure_multi_values(int W) {
+  ensure_multi_r(W);
+  MultiWork &mw = *multi;
+  if (mw.vwidth >= W) return;
+  free_multi_values();
+  try {
+    mw.vA.alloc((size_t)At.nnz * W);
+    mw.vAt.alloc((size_t)At.nnz * W);
+    if (has_P) {
+      mw.vP.alloc((size_t)P.nnz * W);
+      mw.vPdiag.alloc((size_t)n * W);
+    }
+    mw.vstage.alloc((size_t)std::max<long long>(At.nnz, has_P ? nnzP_up : 0));
+  } catch (...) {
+    free_multi_values();
+    throw;
+  }
+  mw.vwidth = W;
+}
+
+// K columns of values, host arrays in the CSC order of init's A / upper P (AX: nnz(A) x K, PX: nnz(upper P) x K, column-major),
+// into the value blocks at the layout width W of K columns; padding columns 0.  One column is staged at a time (the staging is
+// reused in stream order) and scattered into each block by k_m_upd_gather_block through the maps of ensure_update_maps.  Returns
+// with the stream idle: the caller's arrays may be pageable and reused.
+void LinSys::set_multi_values(int K, int W, const real *AX, size_t ldax, const real *PX, size_t ldpx) {
+  ensure_update_maps(true, has_P);
+  ensure_multi_values(W);
+  MultiWork &mw = *multi;
+  mw.vcols = 0; // a failure below leaves no set in force
+  const long long nza = At.nnz, nzp = has_P ? P.nnz : 0;
+  if (nza > 0) {
+    HIP_CHECK(hipMemsetAsync(mw.vA.p, 0, (size_t)nza * W * sizeof(real), stream));
+    HIP_CHECK(hipMemsetAsync(mw.vAt.p, 0, (size_t)nza * W * sizeof(real), stream));
+  }
+  if (nzp > 0) HIP_CHECK(hipMemsetAsync(mw.vP.p, 0, (size_t)nzp * W * sizeof(real), stream));
+  for (int k = 0; k < K; ++k) {
+    if (nza > 0) {
+      mw.vstage.upload(AX + (size_t)k * ldax, (size_t)nza, stream);
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_upd_gather_block<MW>, dim3(upd_grid(nza)), dim3(SCSAMD_BLOCK), 0, stream,
+                                           (const real *)mw.vstage.p, (const eoff *)nullptr, mw.vAt.p, nza, k));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_upd_gather_block<MW>, dim3(upd_grid(nza)), dim3(SCSAMD_BLOCK), 0, stream,
+                                           (const real *)mw.vstage.p, (const eoff *)upd_rpos.p, mw.vA.p, nza, k));
+    }
+    if (nzp > 0) {
+      mw.vstage.upload(PX + (size_t)k * ldpx, (size_t)nnzP_up, stream);
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_upd_gather_block<MW>, dim3(upd_grid(nzp)), dim3(SCSAMD_BLOCK), 0, stream,
+                                           (const real *)mw.vstage.p, (const eoff *)upd_fsrc.p, mw.vP.p, nzp, k));
+    }
+  }
+  if (has_P) {
+    CsrView pv = P.view();
+    pv.val = nullptr;
+    const ValBlk<true> vb{mw.vP.p, (eoff)P.bias};
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_upd_pdiag<MW>, dim3(vec_grid((long long)n * W)), dim3(SCSAMD_BLOCK), 0, stream, pv, vb, mw.vPdiag.p));
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream));
+  mw.vcols = K;
+}
+
+// Minv(n x W) = the Jacobi preconditioner of every column under its own rx (n x W) / ry (m x W): k_precond per column.
+// vAt (with vPdiag when there is a P): every column under its own values too; the workspace's At.val and Pdiag are not read.
+void LinSys::precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv, const real *vAt, const real *vPdiag) {
+  CsrView v = At.view();
+  const int g = vec_grid((long long)n * W);
+  if (vAt) {
+    v.val = nullptr;
+    const ValBlk<true> vb{vAt, (eoff)At.bias};
+    const real *pd = has_P ? vPdiag : nullptr;
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_precond<MW, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, stream, v, rxb, ryb, pd, Minv, vb));
+    return;
+  }
   const real *pd = has_P ? Pdiag.p : nullptr;
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_precond<MW>, dim3(vec_grid((long long)n * W)), dim3(SCSAMD_BLOCK), 0, stream, v, rxb, ryb, pd, Minv));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_precond<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, v, rxb, ryb, pd, Minv, ValBlk<false>{}));
 }
 
 // G X on blocks (private.c:106-119 per column); dot_partials as in launch_spmm's EPI_GP.  rxb / ryb (both or neither): R_x / R_y
-// per column as n x W / m x W blocks instead of the workspace's own.
+// per column as n x W / m x W blocks instead of the workspace's own.  vA / vAt / vP (all, vP with P only, or none): every column
+// its own values of A, A' and P (value blocks at width W) instead of the workspace's; needs rxb / ryb.
 void LinSys::mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip, const real *rxb,
-                               const real *ryb) {
+                               const real *ryb, const real *vA, const real *vAt, const real *vP) {
   MultiWork &mw = *multi;
   real *tmpb = mw.gt.p + (size_t)n * mw.width;
   const bool percol = rxb != nullptr;
   EpiArgs e1{percol ? ryb : ry.p, nullptr, nullptr, nullptr};
-  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip, percol);
+  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip, percol, vA);
   if (has_P) {
     EpiArgs ep{nullptr, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_PLAIN, P, X, mw.Pp.p, ep, cskip, allskip);
+    launch_spmm(W, EPI_PLAIN, P, X, mw.Pp.p, ep, cskip, allskip, false, vP);
   }
   EpiArgs e2{percol ? rxb : rx.p, X, has_P ? mw.Pp.p : nullptr, dot_partials};
-  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip, percol);
+  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip, percol, vAt);
   n_matvecs++;
 }
 
@@ -398,6 +536,10 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
   const bool warm = a.s != nullptr;
   const bool percol = a.rx != nullptr; // every column under its own R_x / R_y / preconditioner: the workspace's rx, ry, M are not read
   if (percol != (a.ry != nullptr) || percol != (a.Minv != nullptr)) throw HipError("scs_amd: per-column R needs rx, ry and Minv together");
+  // every column its own values of A, A' and P: the workspace's A.val, At.val, P.val (and, with percol, rx, ry, M) are read nowhere below
+  const bool vcol = a.vA != nullptr;
+  if (vcol != (a.vAt != nullptr) || (vcol && has_P) != (a.vP != nullptr)) throw HipError("scs_amd: per-column values need vA, vAt and, with P, vP");
+  if (vcol && !percol) throw HipError("scs_amd: per-column values run under per-column R");
   real *const bx = a.bx, *const by = a.by;
   const int gv = vec_grid((long long)n * W), gnm = vec_grid(((long long)n + m) * W);
   CgCtlM *c = mw.ctl.p;
@@ -427,9 +569,9 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
                                          mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
   { // b_x += A' R_y^-1 r_y   (private.c:305)
     EpiArgs e{nullptr, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_ACC, At, tmpb, bx, e, zero, all);
+    launch_spmm(W, EPI_ACC, At, tmpb, bx, e, zero, all, false, a.vAt);
   }
-  if (warm) mat_vec_multi_dev(W, a.s, mw.r.p, nullptr, zero, all, a.rx, a.ry); // r = G s  (private.c:153)
+  if (warm) mat_vec_multi_dev(W, a.s, mw.r.p, nullptr, zero, all, a.rx, a.ry, a.vA, a.vAt, a.vP); // r = G s  (private.c:153)
   if (percol)
     MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_cg_init<MW, true>), dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
                                          mw.z.p, a.Minv, n, mw.part_ztr.p, mw.part_max.p, c));
@@ -448,7 +590,7 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
     if (nb < 1) nb = 1;
     for (int j = 0; j < nb; ++j) {
       const int q = (int)((it + j) & 1);
-      mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all, a.rx, a.ry);
+      mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all, a.rx, a.ry, a.vA, a.vAt, a.vP);
       if (percol)
         MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_cg_update<MW, true>), dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p,
                                              Gp, a.Minv, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
@@ -466,7 +608,7 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
   }
   { // y = R_y^-1 (A x - r_y)   (private.c:313-317)
     EpiArgs e{percol ? a.ry : ry.p, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_NEGDIV, A, bx, by, e, zero, nullptr, percol);
+    launch_spmm(W, EPI_NEGDIV, A, bx, by, e, zero, nullptr, percol, a.vA);
   }
   HIP_CHECK(hipGetLastError());
   int most = 0;

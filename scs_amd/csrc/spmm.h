@@ -24,6 +24,13 @@
 //
 // Per-column masks: `cskip` (W ints, or null) switches single columns off -- their lanes load nothing and store nothing (a
 // stopped column of the block PCG costs no gather); `allskip` (one int, or null) ends the kernel at once.
+//
+// Values per column (VCOL): K systems that share the pattern but not the values.  `ptr` and `idx` are still the workspace's arrays,
+// read once for all columns; the values are a block of nnz x W in the block layout, value (t, col) of stored entry t at
+// (t - bias) * W + col (ValBlk).  Lane `col` of a group reads its own value, so the W lanes of a group read W contiguous values
+// (64 bytes at W = 8 in fp64, a full line at W = 16) next to the W contiguous values they gather; only the indices are staged in
+// LDS.  The sums keep the order and the multiply-add expression of the shared form: a column that holds the workspace's values has
+// the shared form's bits.
 #pragma once
 #include "spmv.h"
 
@@ -104,6 +111,19 @@ template <int W> __device__ __forceinline__ real reduce_partials_col_max(const r
 // epilogues of spmv.h on element (r, col) of a block.  DCOL = false: d (R_x / R_y) is shared by the columns, one value per row.
 // DCOL = true: every column has its own, d is a block in the block layout and element (r, col) is d[o] -- the W lanes of a group
 // read W contiguous values.  The choice is a template parameter: the shared form carries no test for the other.
+// The values of a product: shared by the columns (A.val of the CsrView; nothing more is carried) or one per column.  v: the nnz x W
+// value block; bias: what the stored entry positions carry over the plain ones (CsrDev::bias, the DLONG test hook) -- the block is
+// indexed by the plain position.  The choice is a template parameter, as for DCOL.
+template <bool VCOL> struct ValBlk {};
+template <> struct ValBlk<true> {
+  const real *v;
+  eoff bias;
+};
+template <int W> __device__ __forceinline__ real blk_val(const ValBlk<false> &, const real *val, eoff t, int) { return val[t]; }
+template <int W> __device__ __forceinline__ real blk_val(const ValBlk<true> &vb, const real *, eoff t, int col) {
+  return vb.v[(size_t)(t - vb.bias) * W + col];
+}
+
 template <int EPI, int W>
 __device__ __forceinline__ real epi_init_blk(const EpiArgs &e, const real *y, size_t o) {
   if (EPI == EPI_GP) return e.y0 ? e.y0[o] : (real)0;
@@ -125,16 +145,18 @@ __device__ __forceinline__ void epi_apply_blk(const EpiArgs &e, real *y, int r, 
 
 // Y(rows x W) (op)= A X(cols x W).  EPI_GP: e.partial[blockIdx.x * W + k] receives the workgroup's part of column k's xin . y.
 // DCOL (EPI_DIV, EPI_GP, EPI_NEGDIV): e.d is a rows x W block, one divisor / multiplier per column (epi_apply_blk).
-template <int W, int EPI, bool DCOL = false>
+// VCOL: every column its own values of the matrix, vb.v (ValBlk); A.val is not read and no value is staged in LDS.
+template <int W, int EPI, bool DCOL = false, bool VCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, const real *__restrict__ X, real *Y, EpiArgs e,
-                                                                 const int *cskip, const int *allskip) {
+                                                                 const int *cskip, const int *allskip, ValBlk<VCOL> vb) {
   constexpr int G = SCSAMD_WAVE / W;
   constexpr int STAGE = SPMM_STAGE_PER_ROW * G; // entries a wave stages per pass
   __shared__ real red[(SCSAMD_BLOCK / SCSAMD_WAVE) * W];
-  __shared__ real sval_all[SCSAMD_BLOCK / SCSAMD_WAVE][STAGE];
+  __shared__ real sval_all[SCSAMD_BLOCK / SCSAMD_WAVE][VCOL ? 1 : STAGE]; // VCOL: never referenced, so no LDS is allocated for it
   __shared__ int sidx_all[SCSAMD_BLOCK / SCSAMD_WAVE][STAGE];
   real *sval = sval_all[threadIdx.x >> 6];
   int *sidx = sidx_all[threadIdx.x >> 6];
+  (void)sval;
   if (allskip && *allskip) return; // the same word for every lane of the grid
   const int lane = threadIdx.x & 63, col = lane & (W - 1), g = lane / W;
   const bool on = !(cskip && cskip[col]);
@@ -163,7 +185,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
       const int cnt = (int)(zend - a0);
       for (int t = lane; t < cnt; t += SCSAMD_WAVE) {
         sidx[t] = A.idx[a0 + t];
-        sval[t] = A.val[a0 + t];
+        if constexpr (!VCOL) sval[t] = A.val[a0 + t];
       }
       __builtin_amdgcn_wave_barrier(); // LDS operations of one wave complete in issue order: no workgroup barrier is needed
       if (has) {
@@ -174,16 +196,34 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
         // four gathers in flight per lane; the sum keeps index order.  (Eight in flight with the slots past the row's end
         // predicated off measured slower at W >= 8, 480 against 440 us at W = 8: the latency of a lane's chain is not what
         // bounds the product; profiles/multi_rhs.md.)
-        for (; k + 4 <= kz; k += 4) {
-          const int i0 = sidx[k], i1 = sidx[k + 1], i2 = sidx[k + 2], i3 = sidx[k + 3];
-          const real x0 = X[(size_t)i0 * W + col], x1 = X[(size_t)i1 * W + col], x2 = X[(size_t)i2 * W + col],
-                     x3 = X[(size_t)i3 * W + col];
-          acc += sval[k] * x0;
-          acc += sval[k + 1] * x1;
-          acc += sval[k + 2] * x2;
-          acc += sval[k + 3] * x3;
+        if constexpr (VCOL) {
+          // the lane's own values: W contiguous ones per entry over the lanes of the group, four value loads in flight beside
+          // the four gathers
+          const real *vrow = vb.v + (size_t)(a0 - vb.bias) * W + col;
+          for (; k + 4 <= kz; k += 4) {
+            const int i0 = sidx[k], i1 = sidx[k + 1], i2 = sidx[k + 2], i3 = sidx[k + 3];
+            const real v0 = vrow[(size_t)k * W], v1 = vrow[(size_t)(k + 1) * W], v2 = vrow[(size_t)(k + 2) * W],
+                       v3 = vrow[(size_t)(k + 3) * W];
+            const real x0 = X[(size_t)i0 * W + col], x1 = X[(size_t)i1 * W + col], x2 = X[(size_t)i2 * W + col],
+                       x3 = X[(size_t)i3 * W + col];
+            acc += v0 * x0;
+            acc += v1 * x1;
+            acc += v2 * x2;
+            acc += v3 * x3;
+          }
+          for (; k < kz; ++k) acc += vrow[(size_t)k * W] * X[(size_t)sidx[k] * W + col];
+        } else {
+          for (; k + 4 <= kz; k += 4) {
+            const int i0 = sidx[k], i1 = sidx[k + 1], i2 = sidx[k + 2], i3 = sidx[k + 3];
+            const real x0 = X[(size_t)i0 * W + col], x1 = X[(size_t)i1 * W + col], x2 = X[(size_t)i2 * W + col],
+                       x3 = X[(size_t)i3 * W + col];
+            acc += sval[k] * x0;
+            acc += sval[k + 1] * x1;
+            acc += sval[k + 2] * x2;
+            acc += sval[k + 3] * x3;
+          }
+          for (; k < kz; ++k) acc += sval[k] * X[(size_t)sidx[k] * W + col];
         }
-        for (; k < kz; ++k) acc += sval[k] * X[(size_t)sidx[k] * W + col];
         epi_apply_blk<EPI, W, DCOL>(e, Y, r, o, acc, dot);
       }
       __builtin_amdgcn_wave_barrier();
@@ -196,7 +236,8 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
       eoff k = a;
       for (; k + 4 <= z; k += 4) {
         const int i0 = A.idx[k], i1 = A.idx[k + 1], i2 = A.idx[k + 2], i3 = A.idx[k + 3];
-        const real v0 = A.val[k], v1 = A.val[k + 1], v2 = A.val[k + 2], v3 = A.val[k + 3];
+        const real v0 = blk_val<W>(vb, A.val, k, col), v1 = blk_val<W>(vb, A.val, k + 1, col), v2 = blk_val<W>(vb, A.val, k + 2, col),
+                   v3 = blk_val<W>(vb, A.val, k + 3, col);
         const real x0 = X[(size_t)i0 * W + col], x1 = X[(size_t)i1 * W + col], x2 = X[(size_t)i2 * W + col],
                    x3 = X[(size_t)i3 * W + col];
         acc += v0 * x0;
@@ -204,7 +245,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
         acc += v2 * x2;
         acc += v3 * x3;
       }
-      for (; k < z; ++k) acc += A.val[k] * X[(size_t)A.idx[k] * W + col];
+      for (; k < z; ++k) acc += blk_val<W>(vb, A.val, k, col) * X[(size_t)A.idx[k] * W + col];
       epi_apply_blk<EPI, W, DCOL>(e, Y, r, o, acc, dot);
     }
     // long rows of this pass, one after the other, by the whole wave
@@ -215,7 +256,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void csr_block_kernel(CsrView A, cons
       const eoff al = __shfl(a, src, 64), zl = __shfl(z, src, 64);
       real part = 0;
       if (on)
-        for (eoff k = al + g; k < zl; k += G) part += A.val[k] * X[(size_t)A.idx[k] * W + col];
+        for (eoff k = al + g; k < zl; k += G) part += blk_val<W>(vb, A.val, k, col) * X[(size_t)A.idx[k] * W + col];
       part = col_wave_sum<W>(part);
       if (on && g == gl) {
         const int rr = (int)(base + gl);

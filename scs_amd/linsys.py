@@ -6,7 +6,9 @@ Solves the reduced KKT system of SCS on the GPU,
 
 for one right-hand side (`solve`, scs_solve_lin_sys) or for a block of them at once (`solve_many`,
 scs_amd_solve_lin_sys_multi: K independent PCG solves in lock step that share A, P and diag_r; with `diag_r=` every column
-runs under its own diag_r, scs_amd_solve_lin_sys_multi_r -- a sweep over rho, scale or regularisation as one block).  One workspace lives for the
+runs under its own diag_r, scs_amd_solve_lin_sys_multi_r -- a sweep over rho, scale or regularisation as one block; after
+`set_values_many`, `own_values=True` gives every column its own values of A and P on the shared pattern,
+scs_amd_solve_lin_sys_multi_v -- time-varying or scenario-dependent coefficients as one block).  One workspace lives for the
 lifetime of the object (scs_init_lin_sys_work once, scs_free_lin_sys_work on close / garbage collection).  Host code only: every
 flop is in the library.
 
@@ -48,9 +50,30 @@ def check_block(n, m, B, S=None, tol=1e-9, DR=None):
     return K
 
 
+def check_values_block(nnz_a, nnz_p, A_values, P_values):
+    """Shapes of a block of matrix values, checked before the library is called (needs no workspace): A_values (nnz_a, K) with
+    1 <= K <= 16, P_values (nnz_p, K) exactly when the workspace has a P (nnz_p is None without one), every entry finite.
+    Returns K."""
+    A_values = np.asarray(A_values)
+    if A_values.ndim != 2 or A_values.shape[0] != nnz_a or not 1 <= A_values.shape[1] <= 16:
+        raise ValueError(f"A_values must have shape ({nnz_a}, K) with 1 <= K <= 16, got {A_values.shape}")
+    K = A_values.shape[1]
+    if (P_values is None) != (nnz_p is None):
+        raise ValueError("P_values must be given exactly when the workspace has a P")
+    if P_values is not None:
+        P_values = np.asarray(P_values)
+        if P_values.ndim != 2 or P_values.shape != (nnz_p, K):
+            raise ValueError(f"P_values must have shape ({nnz_p}, {K}), got {P_values.shape}")
+    for v in (A_values, P_values):
+        if v is not None and not np.all(np.isfinite(v)):
+            raise ValueError("matrix values must be finite")
+    return K
+
+
 class LinSys:
     def __init__(self, A, diag_r, P=None, dtype="f64"):
         self._w = None
+        self._vcols = 0  # columns of the set_values_many in force
         self._lib = capi.load("libscsamd_f32.so" if dtype in ("f32", np.float32) else "libscsamd.so")
         T = self._T = self._lib._scs_types
         import scipy.sparse as sp
@@ -88,22 +111,62 @@ class LinSys:
             raise RuntimeError("scs_solve_lin_sys failed")
         return out
 
-    def solve_many(self, B, S=None, tol=1e-9, diag_r=None):
+    def set_values_many(self, A_values, P_values=None):
+        """scs_amd_linsys_set_values_multi: the values of K (1 .. 16) systems on the pattern given at construction, for
+        `solve_many(..., own_values=True)`.  A_values (nnz(A), K): column k = the values of A_k in the CSC order of A; P_values
+        (nnz(upper P), K), exactly when the workspace has a P.  The workspace's own matrices, `solve` and the other forms of
+        `solve_many` are not affected.  ValueError for bad shapes, a non-finite value or a refusal of the library."""
+        w, T = self._work(), self._T
+        nnz_p = None if self._prob.matP is None else len(self._prob.Pi)
+        K = check_values_block(len(self._prob.Ai), nnz_p, A_values, P_values)
+        ax = np.asfortranarray(A_values, dtype=T.np_float)
+        px = None if P_values is None else np.asfortranarray(P_values, dtype=T.np_float)
+        for v in (ax, px):
+            if v is not None and not np.all(np.isfinite(v)):  # an entry that overflows in the library's precision
+                raise ValueError("matrix values must be finite in the library's precision")
+        rc = self._lib.scs_amd_linsys_set_values_multi(w, K, ax.ctypes.data_as(T.fp), max(1, ax.shape[0]),
+                                                       px.ctypes.data_as(T.fp) if px is not None else None,
+                                                       max(1, px.shape[0]) if px is not None else 0)
+        if rc != 0:
+            raise ValueError("scs_amd_linsys_set_values_multi refused the values")
+        self._vcols = K
+
+    def free_values_many(self):
+        """scs_amd_linsys_free_values_multi: releases the device memory of `set_values_many`; a later set call allocates again."""
+        self._lib.scs_amd_linsys_free_values_multi(self._work())
+        self._vcols = 0
+
+    def solve_many(self, B, S=None, tol=1e-9, diag_r=None, own_values=False):
         """scs_amd_solve_lin_sys_multi: column k of B (n + m, K) -> [x; y] of that column, as `solve` would give it; S (n, K) warm
         starts or None; tol a scalar or one per column.  Returns (XY, iters): the solutions (n + m, K) and the PCG iteration count
         of every column.  diag_r (n + m, K): column k is solved under its own diag_r = diag_r[:, k], as `update_diag_r` followed by
         `solve` would give it (scs_amd_solve_lin_sys_multi_r); the workspace's own diag_r is neither used nor changed.
+        own_values: column k is solved with the values of A and P given to `set_values_many` as column k, as `update_values`
+        followed by the above would give it (scs_amd_solve_lin_sys_multi_v); K must equal the set call's; diag_r None = the
+        workspace's diag_r in every column.  The workspace's own matrices are neither used nor changed.
         B, S, tol and diag_r are not modified."""
         w, T = self._work(), self._T
         K = check_block(self.n, self.m, B, S, tol, diag_r)
+        if own_values and K != self._vcols:
+            raise ValueError(f"own_values needs a set_values_many of {K} columns first (in force: {self._vcols})")
         out = np.array(B, dtype=T.np_float, order="F", copy=True)
         Sv = None if S is None else np.asfortranarray(S, dtype=T.np_float)
         tv = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, dtype=T.np_float), (K,)))
         iters = np.zeros(K, dtype=T.np_int)
+        Dv = None
         if diag_r is not None:
             Dv = np.asfortranarray(diag_r, dtype=T.np_float)
             if not np.all(Dv > 0):  # an entry that underflows in the library's precision
                 raise ValueError("diag_r must be positive in the library's precision")
+        if own_values:
+            rc = self._lib.scs_amd_solve_lin_sys_multi_v(w, K, Dv.ctypes.data_as(T.fp) if Dv is not None else None, self.n + self.m,
+                                                         out.ctypes.data_as(T.fp), self.n + self.m,
+                                                         Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
+                                                         tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
+            if rc != 0:
+                raise ValueError("scs_amd_solve_lin_sys_multi_v refused the call")
+            return out, iters.astype(np.int64)
+        if diag_r is not None:
             rc = self._lib.scs_amd_solve_lin_sys_multi_r(w, K, Dv.ctypes.data_as(T.fp), self.n + self.m, out.ctypes.data_as(T.fp),
                                                          self.n + self.m, Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
                                                          tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
