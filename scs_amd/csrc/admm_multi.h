@@ -22,7 +22,7 @@
 //
 // Two entries, one loop.  scs_amd_solve_family: the columns share the workspace's diag_r (the instantiations with PERCOL / PC =
 // false).  scs_amd_solve_family_scaled: column k runs under its own diag_r_k, built from its own scale, in an l x W block R whose x
-// and y rows are the rx / ry blocks of the per-column block solve (MultiRhs::rx / ry / Minv, linsys_multi.h); the glue kernels read
+// and y rows are the rx / ry blocks of the per-column block solve (MultiOp::rx / ry / Minv, linsys.h); the glue kernels read
 // R[f] where the shared form reads R[f / W], in the same expressions, so equal scales give the shared form's bits.  With
 // adaptive_scale the column runs update_scale (admm.hip, :1164-1241) on its own residuals where the single loop runs it -- at a
 // check, after the convergence test, before the dual update.  For the columns whose scale changed (FamCtl::upd), in this order:
@@ -49,7 +49,7 @@
 //     column started running -- has passed;
 //   * its result is taken out (k_f_col_out: its x, y, s in one contiguous record, not the l x W blocks) and returned at once; the
 //     lowest free slot takes the next problem of the queue, in index order (k_f_col_in: its b, c, v and zeros in its u, u_t, rsk, cw,
-//     warm, g; its g from update_g with every other column skipped; with own scales its R, preconditioner and box r_y through the
+//     warm, g; its g from family_update_g with every other column skipped; with own scales its R, preconditioner and box r_y through the
 //     FamCtl::upd path of a scale update);
 //   * THAT PROBLEM STARTS AT THE SMALLEST MULTIPLE OF CONVERGED_INTERVAL GREATER THAN i, so every start is a multiple of 25: all
 //     running columns reach their checks in the same global iterations, one residual evaluation and one read-back serve all of
@@ -434,17 +434,6 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_final(const real *part
 // ============================================================================
 // host control: solve_begin / solve_steps / populate_residuals / has_converged / finalize per column
 // ============================================================================
-#define FAM_DISPATCH(W_, CALL)                                                                                         \
-  do {                                                                                                                 \
-    switch (W_) {                                                                                                      \
-    case 2: { constexpr int MW = 2; CALL; } break;                                                                     \
-    case 4: { constexpr int MW = 4; CALL; } break;                                                                     \
-    case 8: { constexpr int MW = 8; CALL; } break;                                                                     \
-    case 16: { constexpr int MW = 16; CALL; } break;                                                                   \
-    default: throw HipError("scs_amd: bad block width");                                                               \
-    }                                                                                                                  \
-  } while (0)
-
 // Family state: belongs to scs_amd_solve_family only.  Blocks at the largest width used so far (a narrower chunk uses the front
 // of each buffer at its own width), allocated at the first call, freed with the workspace.
 struct FamilyWork {
@@ -461,7 +450,7 @@ struct FamilyWork {
   std::vector<real> hblk, hblk2, col_x, col_y, col_s; // host staging
   // scs_amd_solve_family_scaled only, allocated at its first call (family_ensure_r): every column its own diag_r
   int rwidth = 0;
-  DevBuf<real> R;    // l x W: [R_x rows | R_y rows | the tau row]; its x and y parts are the rx / ry blocks MultiRhs takes
+  DevBuf<real> R;    // l x W: [R_x rows | R_y rows | the tau row]; its x and y parts are the rx / ry blocks of MultiOp::r_rows
   DevBuf<real> Minv; // n x W: the Jacobi preconditioner of every column under its own R (precond_multi_blocks)
   // scs_amd_solve_family_stream only, allocated at its first call (family_ensure_stream): the records of k_f_col_in / k_f_col_out,
   // column k's at k * (m + n + l) / k * (n + 2 m), with their host copies, and the counters of the last stream call
@@ -559,12 +548,12 @@ static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter, u
   w->ls.launch_spmm(W, EPI_PLAIN, w->ls.At, y, f.aty.p, e, frozen, nullptr);
   if (w->has_P) w->ls.launch_spmm(W, EPI_PLAIN, w->ls.P, x, f.px.p, e, frozen, nullptr);
   const int gm = glue_grid((long long)m * W), gn = glue_grid((long long)n * W);
-  FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_primal<MW>, dim3(gm), dim3(SCSAMD_BLOCK), 0, st, f.ax.p, s, y, f.b.p, w->D.p, tau_row, m,
-                                     f.part.p, PSTRIDE, f.ctl.p));
-  FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_dual<MW>, dim3(gn), dim3(SCSAMD_BLOCK), 0, st, w->has_P ? f.px.p : (const real *)nullptr,
-                                     f.aty.p, x, f.c.p, w->E.p, tau_row, n, f.part.p, PSTRIDE, f.ctl.p));
-  FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_final<MW>, dim3(1), dim3(SCSAMD_BLOCK), 0, st, f.part.p, PSTRIDE, gm, gn, tau_row, kap_row,
-                                     f.qout.p, f.ctl.p));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_primal<MW>, dim3(gm), dim3(SCSAMD_BLOCK), 0, st, f.ax.p, s, y, f.b.p, w->D.p, tau_row, m,
+                                       f.part.p, PSTRIDE, f.ctl.p));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_dual<MW>, dim3(gn), dim3(SCSAMD_BLOCK), 0, st, w->has_P ? f.px.p : (const real *)nullptr,
+                                       f.aty.p, x, f.c.p, w->E.p, tau_row, n, f.part.p, PSTRIDE, f.ctl.p));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_final<MW>, dim3(1), dim3(SCSAMD_BLOCK), 0, st, f.part.p, PSTRIDE, gm, gn, tau_row, kap_row,
+                                       f.qout.p, f.ctl.p));
   HIP_CHECK(hipMemcpyAsync(f.hq.p, f.qout.p, (size_t)NQ * W * sizeof(real), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   w->cone_timer.harvest(); // stream is idle here
@@ -678,6 +667,33 @@ static void family_return(ScsWork *w, const FamCol &col, bool own_scale, int tim
   if (w->stgs.verbose) print_summary_row(col.r_o, col.iter, own_scale ? col.scale : w->stgs.scale, (solve_ms + w->setup_time) / 1e3);
 }
 
+// the operator of a family's block solves: with own scales the x and y rows of f.R and f.Minv, else the workspace's shared R
+static MultiOp family_op(const ScsWork *w, int W, bool own_r) {
+  return own_r ? MultiOp::r_rows(w->fam->R.p, (size_t)w->n * W, w->fam->Minv.p) : MultiOp::shared();
+}
+
+// the R of every column (padding: 1) from the scales of the control record, its preconditioner and the box cone's copy of its r_y
+static void family_apply_scales(ScsWork *w, int W, int K) {
+  FamilyWork &f = *w->fam;
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_set_diag_r<MW>, dim3(glue_grid((long long)w->l * W)), dim3(SCSAMD_BLOCK), 0, w->stream, f.R.p, w->n,
+                                         w->m, (int)w->k.z, w->stgs.rho_x, K, f.ctl.p));
+  w->ls.precond_multi_blocks(W, family_op(w, W, true), f.Minv.p);
+  w->cone.set_multi_ry(f.R.p + (size_t)w->n * W, W);
+}
+
+// update_work_cache per column: g = (R + M)^-1 [c; -b] to CG_BEST_TOL (:1118-1128).  `skip` (W ints on the device): the columns
+// whose g stays as it is -- not one bit of theirs is read or written
+static void family_update_g(ScsWork *w, int W, int K, bool own_r, const int *skip) {
+  FamilyWork &f = *w->fam;
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(glue_grid((long long)(w->n + w->m) * W)), dim3(SCSAMD_BLOCK), 0, w->stream, f.g.p,
+                                         f.c.p, f.b.p, w->n, w->m, skip));
+  real tolv[MULTI_W_MAX];
+  for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = (real)CG_BEST_TOL;
+  MultiRhs a(f.g.p, f.g.p + (size_t)w->n * W, nullptr, family_op(w, W, own_r));
+  a.pre_stopped = skip;
+  w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
+}
+
 // K (1 <= K <= W) problems as one block of width W.  B / Cc: column-major host data of this chunk.  Returns SCS_SIGINT when
 // interrupted (the unfinished columns are then filled by fail_out), 0 otherwise; throws on a HIP failure.
 // PC = false: scs_amd_solve_family, the columns share the workspace's diag_r.  PC = true: scs_amd_solve_family_scaled, column k
@@ -718,14 +734,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     cols[k].upd = PC;
   }
   family_upload_ctl(w, W, K, cols, PC ? 1 : 0);
-  // the R of every column (padding: 1), its preconditioner and the box cone's copy of its r_y
-  auto apply_scales = [&]() {
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_set_diag_r<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.R.p, n, m, (int)w->k.z, w->stgs.rho_x, K,
-                                       f.ctl.p));
-    w->ls.precond_multi_blocks(W, f.R.p, f.R.p + nw, f.Minv.p);
-    w->cone.set_multi_ry(f.R.p + nw, W);
-  };
-  if (PC) apply_scales();
+  if (PC) family_apply_scales(w, W, K);
   for (int k = 0; k < K; ++k) cols[k].upd = false;
   HIP_CHECK(hipStreamSynchronize(st)); // the staging vectors are reused below
 
@@ -754,18 +763,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   // ---- update_work_cache per column: g = (R + M)^-1 [c; -b] to CG_BEST_TOL (:1118-1128)
   const int *frozen = f.ctl.p->frozen;
   real tolv[MULTI_W_MAX];
-  // `skip` (W ints on the device): the columns whose g stays as it is -- not one bit of theirs is read or written
-  auto update_g = [&](const int *skip) {
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.g.p, f.c.p, f.b.p, n, m, skip));
-    for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = (real)CG_BEST_TOL;
-    MultiRhs a;
-    a.bx = f.g.p;
-    a.by = f.g.p + nw;
-    a.pre_stopped = skip;
-    if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
-    w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
-  };
-  update_g(frozen);
+  family_update_g(w, W, K, PC, frozen);
 
   // ---- the loop of src/scs.c:1356-1455 on blocks
   real *part = f.part.p, *nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, *warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
@@ -774,17 +772,13 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   bool sigint = false;
   for (; i < max_iters && running > 0; ++i) {
     const int do_norm = i >= FEASIBLE_ITERS;
-    if (do_norm) FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
-    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
-                                       f.warm.p, n, l, nrm_part, gl, warm_part, do_norm, f.ctl.p));
+    if (do_norm) MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
+                                         f.warm.p, n, l, nrm_part, gl, warm_part, do_norm, f.ctl.p));
     { // the linear system (:763), every column on its own tolerance schedule (:745-762)
       const double tl = now_ms();
-      MultiRhs a;
-      a.bx = f.u_t.p;
-      a.by = f.u_t.p + nw;
-      a.s = f.warm.p;
+      MultiRhs a(f.u_t.p, f.u_t.p + nw, f.warm.p, family_op(w, W, PC));
       a.pre_stopped = frozen;
-      if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
       if (w->cg_tol_override > 0) {
         for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
       } else {
@@ -798,10 +792,10 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     }
     const int feas = i < FEASIBLE_ITERS;
     if (!feas)
-      FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
-                                         n + m, part, PSTRIDE, f.ctl.p));
-    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
-                                       f.cw.p, n, l, part, gnm, PSTRIDE, feas, f.ctl.p));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
+                                           n + m, part, PSTRIDE, f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
+                                         f.cw.p, n, l, part, gnm, PSTRIDE, feas, f.ctl.p));
     int cslot = -1;
     if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
     if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true); // the box cone under the column's own r_y
@@ -809,8 +803,8 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     w->cone_timer.stop(cslot, st);
     w->cone_projs++;
     const bool check = i % CONVERGED_INTERVAL == 0;
-    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
-                                       f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
+                                         f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
     if (!check) continue;
     if (interrupted()) { // :1400-1403
       sigint = true;
@@ -851,13 +845,13 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       break;
     }
     if (rescaled) { // update_scale's device half for the columns in upd; of the others not one bit changes
-      apply_scales();
-      update_g(f.ctl.p->keep);
-      FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
+      family_apply_scales(w, W, K);
+      family_update_g(w, W, K, PC, f.ctl.p->keep);
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
       for (int k = 0; k < K; ++k) cols[k].upd = false;
     }
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
-                                       f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
+                                         f.ctl.p));
   }
   HIP_CHECK(hipStreamSynchronize(st));
 
@@ -998,25 +992,8 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
   double t_lin = 0;
   int next = 0, busy = 0, running = 0; // the queue's head; slots that hold a problem; slots whose column runs
 
-  auto apply_scales = [&]() {
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_set_diag_r<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.R.p, n, m, (int)w->k.z, w->stgs.rho_x, K,
-                                       f.ctl.p));
-    w->ls.precond_multi_blocks(W, f.R.p, f.R.p + nw, f.Minv.p);
-    w->cone.set_multi_ry(f.R.p + nw, W);
-  };
-  auto update_g = [&](const int *skip) {
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.g.p, f.c.p, f.b.p, n, m, skip));
-    for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = (real)CG_BEST_TOL;
-    MultiRhs a;
-    a.bx = f.g.p;
-    a.by = f.g.p + nw;
-    a.pre_stopped = skip;
-    if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
-    w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
-  };
-
   // The lowest free slots take the next problems of the queue, which start at global iteration `start`.  The stream is idle on
-  // entry (the control record is rewritten) and has been waited on after the staging upload on return (update_g waits).
+  // entry (the control record is rewritten) and has been waited on after the staging upload on return (family_update_g waits).
   auto fill = [&](int start, bool first) {
     unsigned mask = 0;
     for (int k = 0; k < K && next < nprob; ++k) {
@@ -1044,7 +1021,7 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
     }
     if (!mask) return;
     family_upload_ctl(w, W, K, cols, first && PC ? 1 : 0);
-    if (PC) apply_scales();
+    if (PC) family_apply_scales(w, W, K);
     if (warm_start) { // solve_begin per problem, under its own R_y
       if (PC || hr.empty()) {
         hr.resize(PC ? lw : (size_t)l);
@@ -1063,15 +1040,15 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
     for (int k = 0; k < K; ++k)
       if ((mask >> k) & 1u) HIP_CHECK(hipMemcpyAsync(f.stage.p + (size_t)k * rec_in, f.hstage.data() + (size_t)k * rec_in, rec_in * sizeof(real),
                                                      hipMemcpyHostToDevice, st));
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_col_in<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.stage.p, mask, f.b.p, f.c.p, f.v.p, f.u.p,
-                                       f.u_t.p, f.rsk.p, f.cw.p, f.warm.p, f.g.p, n, m));
-    update_g(first ? frozen : f.ctl.p->keep); // update_work_cache for the new columns alone (:1118-1128)
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_col_in<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.stage.p, mask, f.b.p, f.c.p, f.v.p, f.u.p,
+                                         f.u_t.p, f.rsk.p, f.cw.p, f.warm.p, f.g.p, n, m));
+    family_update_g(w, W, K, PC, first ? frozen : f.ctl.p->keep); // update_work_cache for the new columns alone (:1118-1128)
     for (int k = 0; k < K; ++k) cols[k].upd = false;
   };
 
   // The columns in `mask` have ended: their (x, y, s) out of the blocks, their results to the caller, their slots free.
   auto take_out = [&](unsigned mask) {
-    FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_col_out<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.outb.p, mask, f.u.p, f.rsk.p, n, m));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_col_out<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.outb.p, mask, f.u.p, f.rsk.p, n, m));
     for (int k = 0; k < K; ++k)
       if ((mask >> k) & 1u) HIP_CHECK(hipMemcpyAsync(f.hout.data() + (size_t)k * rec_out, f.outb.p + (size_t)k * rec_out, rec_out * sizeof(real),
                                                      hipMemcpyDeviceToHost, st));
@@ -1133,17 +1110,13 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       if (i - cols[k].start < FEASIBLE_ITERS) first_mask |= 1 << k;
       else norm_mask |= 1 << k;
     }
-    if (norm_mask) FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
-    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
-                                       f.warm.p, n, l, nrm_part, gl, warm_part, norm_mask, f.ctl.p));
+    if (norm_mask) MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
+                                         f.warm.p, n, l, nrm_part, gl, warm_part, norm_mask, f.ctl.p));
     {
       const double tl = now_ms();
-      MultiRhs a;
-      a.bx = f.u_t.p;
-      a.by = f.u_t.p + nw;
-      a.s = f.warm.p;
+      MultiRhs a(f.u_t.p, f.u_t.p + nw, f.warm.p, family_op(w, W, PC));
       a.pre_stopped = frozen;
-      if (PC) a.rx = f.R.p, a.ry = f.R.p + nw, a.Minv = f.Minv.p;
       for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = 0, wsc[k] = 1;
       if (w->cg_tol_override > 0) {
         for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
@@ -1161,10 +1134,10 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       t_lin += now_ms() - tl;
     }
     if (norm_mask)
-      FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
-                                         n + m, part, PSTRIDE, f.ctl.p));
-    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
-                                       f.cw.p, n, l, part, gnm, PSTRIDE, first_mask, f.ctl.p));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
+                                           n + m, part, PSTRIDE, f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
+                                         f.cw.p, n, l, part, gnm, PSTRIDE, first_mask, f.ctl.p));
     int cslot = -1;
     if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
     if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true);
@@ -1172,8 +1145,8 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
     w->cone_timer.stop(cslot, st);
     w->cone_projs++;
     const bool check = i % CONVERGED_INTERVAL == 0; // every start is a multiple of CONVERGED_INTERVAL: all columns check together
-    FAM_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
-                                       f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
+                                         f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
     unsigned ended = 0;
     if (check) {
       if (interrupted()) {
@@ -1207,14 +1180,14 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       }
       if (changed || rescaled) family_upload_ctl(w, W, K, cols); // the stream has been waited on and nothing has been enqueued since
       if (rescaled) {
-        apply_scales();
-        update_g(f.ctl.p->keep);
-        FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
+        family_apply_scales(w, W, K);
+        family_update_g(w, W, K, PC, f.ctl.p->keep);
+        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
         for (int k = 0; k < K; ++k) cols[k].upd = false;
       }
       if (running > 0)
-        FAM_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
-                                           f.ctl.p));
+        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
+                                             f.ctl.p));
     }
     unsigned capped = 0; // the column's last iteration: its residuals as they stand after it, as the chunk loop's after its last
     for (int k = 0; k < K; ++k)

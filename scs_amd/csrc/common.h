@@ -65,6 +65,19 @@ inline void hip_check(hipError_t e, const char *what, const char *file, int line
 }
 #define HIP_CHECK(x) ::scsamd::hip_check((x), #x, __FILE__, __LINE__)
 
+// The width switch of everything that works on blocks (linsys_multi.h, admm_multi.h, cones_multi.h): CALL with the layout width
+// W_ (spmm.h: 2, 4, 8 or 16) as the constant MW
+#define MULTI_DISPATCH(W_, CALL)                                                                                       \
+  do {                                                                                                                 \
+    switch (W_) {                                                                                                      \
+    case 2: { constexpr int MW = 2; CALL; } break;                                                                     \
+    case 4: { constexpr int MW = 4; CALL; } break;                                                                     \
+    case 8: { constexpr int MW = 8; CALL; } break;                                                                     \
+    case 16: { constexpr int MW = 16; CALL; } break;                                                                   \
+    default: throw HipError("scs_amd: bad block width");                                                               \
+    }                                                                                                                  \
+  } while (0)
+
 // one zero-fill stream per host thread, owned by a thread_local holder: destroyed when the thread
 // exits and when the thread switches device
 struct FillStream {

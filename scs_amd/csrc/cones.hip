@@ -1293,9 +1293,9 @@ scs_int scs_amd_cone_proj_dual_multi(ScsAmdConeWork *c, scs_int nrhs, scs_float 
       const int g = std::max(1, std::min(2048, ceil_div((long long)m, SCSAMD_BLOCK)));
       if (m) HIP_CHECK(hipMemcpy2DAsync(mc.cols.p, m * sz, Xc, (size_t)ldx * sz, m * sz, (size_t)K, hipMemcpyHostToDevice, c->stream));
       if (r_y) cd.r_stage.upload(r_y, m, c->stream);
-      CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cone_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, c->stream, mc.cols.p, mc.xblk.p, (int)m, K));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cone_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, c->stream, mc.cols.p, mc.xblk.p, (int)m, K));
       cd.proj_dual_multi(mc.xblk.p, W, K, r_y ? cd.r_stage.p : nullptr);
-      CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cone_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, c->stream, mc.cols.p, mc.xblk.p, (int)m, K));
+      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cone_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, c->stream, mc.cols.p, mc.xblk.p, (int)m, K));
       if (m) HIP_CHECK(hipMemcpy2DAsync(Xc, (size_t)ldx * sz, mc.cols.p, m * sz, m * sz, (size_t)K, hipMemcpyDeviceToHost, c->stream));
       const int bad = cd.take_status(c->stream); // synchronises the stream
       HIP_CHECK(hipGetLastError());

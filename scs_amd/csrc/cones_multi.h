@@ -262,18 +262,7 @@ template <int W> __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cone_from_b
   }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------
-#define CONE_MULTI_DISPATCH(W_, CALL)                                                                                  \
-  do {                                                                                                                 \
-    switch (W_) {                                                                                                      \
-    case 2: { constexpr int MW = 2; CALL; } break;                                                                     \
-    case 4: { constexpr int MW = 4; CALL; } break;                                                                     \
-    case 8: { constexpr int MW = 8; CALL; } break;                                                                     \
-    case 16: { constexpr int MW = 16; CALL; } break;                                                                   \
-    default: throw HipError("scs_amd: bad block width");                                                               \
-    }                                                                                                                  \
-  } while (0)
-
+// ---- host side (the width switch is MULTI_DISPATCH, common.h) -------------------------------------------------------------------
 ConeMulti::~ConeMulti() {
   for (BigPsd *b : big) delete b;
 }
@@ -334,9 +323,9 @@ void ConeDev::proj_dual_multi(real *X, int W, int K, const real *r_y) {
   ensure_multi(W);
   ConeMulti &mc = *multi;
   const int g = small_grid((long long)m * W);
-  CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_pre<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_pre<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
   proj_primal_multi(X, W, K, r_y);
-  CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_post<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_moreau_post<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, X, mc.s.p, r_y, m, K));
 }
 
 // the block state back to what ensure_multi leaves: every column position starts its box Newton iteration and its eigenbases cold
@@ -367,7 +356,7 @@ void ConeDev::set_multi_ry(const real *Ry, int W) {
   ConeMulti &mc = *multi;
   if (!mc.ry_cols.p) mc.ry_cols.alloc((size_t)m * W);
   const int gb = std::max(1, std::min(2048, (bsize + CONE_TR - 1) / CONE_TR));
-  CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, Ry, mc.ry_cols.p, m, box_off, box_off + bsize));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, Ry, mc.ry_cols.p, m, box_off, box_off + bsize));
 }
 
 // X (device, m x W block) <- Proj_K of its columns (proj_cone, cones.c:1340-1394, per column), without the Moreau wrapper: what
@@ -378,40 +367,40 @@ void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y, bool own
   ConeMulti &mc = *multi;
   if (own_ry && bsize > 0 && !mc.ry_cols.p) throw HipError("scs_amd: per-column r_y of the box cone has not been set");
   if (z + l > 0)
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_zero_pos<MW>, dim3(small_grid((long long)(z + l) * W)), dim3(SCSAMD_BLOCK), 0, stream, X, z, l));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_zero_pos<MW>, dim3(small_grid((long long)(z + l) * W)), dim3(SCSAMD_BLOCK), 0, stream, X, z, l));
   if (bsize > 0) { // column after column on the column position's Newton start
     const int gb = std::max(1, std::min(2048, (bsize + CONE_TR - 1) / CONE_TR));
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
     const real *rb = r_y ? r_y + box_off : (const real *)nullptr;
     for (int k = 0; k < K; ++k)
       launch_box(mc.cols.p + (size_t)k * m + box_off, mc.box_t.p + k, own_ry ? mc.ry_cols.p + (size_t)k * m + box_off : rb);
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cols_to_rows<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cols_to_rows<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
   }
   if (n_tiny)
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_tiny<MW>, dim3(small_grid((long long)n_tiny * W)), dim3(SCSAMD_BLOCK), 0, stream, X, tiny_off.p,
-                                              tiny_len.p, n_tiny));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_tiny<MW>, dim3(small_grid((long long)n_tiny * W)), dim3(SCSAMD_BLOCK), 0, stream, X, tiny_off.p,
+                                         tiny_len.p, n_tiny));
   if (n_big) {
     const int gt = std::min(n_tiles, 8192);
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_tile_partial<MW>, dim3(gt), dim3(SCSAMD_BLOCK), 0, stream, X, tile_off.p, tile_len.p,
-                                              tile_cone.p, big_off.p, mc.tile_part.p, n_tiles));
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_finalize<MW>, dim3(small_grid((long long)n_big * W)), dim3(SCSAMD_BLOCK), 0, stream, X,
-                                              big_off.p, big_tile0.p, mc.tile_part.p, mc.big_coef.p, n_big));
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_tile_apply<MW>, dim3(gt), dim3(SCSAMD_BLOCK), 0, stream, X, tile_off.p, tile_len.p,
-                                              tile_cone.p, big_off.p, mc.big_coef.p, n_tiles));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_tile_partial<MW>, dim3(gt), dim3(SCSAMD_BLOCK), 0, stream, X, tile_off.p, tile_len.p,
+                                         tile_cone.p, big_off.p, mc.tile_part.p, n_tiles));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_finalize<MW>, dim3(small_grid((long long)n_big * W)), dim3(SCSAMD_BLOCK), 0, stream, X,
+                                         big_off.p, big_tile0.p, mc.tile_part.p, mc.big_coef.p, n_big));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_soc_tile_apply<MW>, dim3(gt), dim3(SCSAMD_BLOCK), 0, stream, X, tile_off.p, tile_len.p,
+                                         tile_cone.p, big_off.p, mc.big_coef.p, n_tiles));
   }
   if (n_psd) {
     const int p0 = psd_row0, gp = std::max(1, std::min(2048, (exp_off - psd_row0 + CONE_TR - 1) / CONE_TR));
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gp), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, p0, exp_off));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gp), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, p0, exp_off));
     // the LDS kernel over the blocks of all W columns in ONE launch (a padding column holds zero blocks: no sweeps)
     const int warm = mc.psd_vprev.p != nullptr && (mc.psd_calls % PSD_WARM_RESET) != 0;
     ++mc.psd_calls;
     launch_psd_lds(mc.cols.p, n_psd * W, mc.psd_off.p, mc.psd_k.p, mc.psd_tscratch.p, mc.psd_vprev.p, warm);
     for (size_t k = 0; k < mc.big.size() && (int)k < K; ++k) mc.big[k]->project(mc.cols.p + k * m, psd_off.p, psd_k.p, status.p, stream);
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cols_to_rows<MW>, dim3(gp), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, p0, exp_off));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cols_to_rows<MW>, dim3(gp), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, p0, exp_off));
   }
   if (ep + ed + psize > 0)
-    CONE_MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_exp_pow<MW>, dim3(small_grid((long long)(ep + ed + psize) * W)), dim3(SCSAMD_BLOCK), 0, stream,
-                                              X + (size_t)exp_off * W, ep, ed, psize, pow_a.p));
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_exp_pow<MW>, dim3(small_grid((long long)(ep + ed + psize) * W)), dim3(SCSAMD_BLOCK), 0, stream,
+                                         X + (size_t)exp_off * W, ep, ed, psize, pow_a.p));
 }
 
 } // namespace scsamd

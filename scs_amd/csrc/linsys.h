@@ -84,6 +84,49 @@ struct ShardHook {
   int (*allreduce)(void *ctx, real *buf, size_t count, int op /* 0 sum, 1 max */, hipStream_t st) = nullptr; // 0 = ok
 };
 
+// The operator of a block solve or block product: what differs from column to column, as blocks in device memory in the layout of
+// spmm.h.  All null = the workspace's shared rx / ry / M and values.  A new per-column quantity is a field here, a line of check()
+// and an argument of the constructors below.
+struct MultiOp {
+  // every column under its own diag_r: R_x (n x W), R_y (m x W) and the preconditioner built from them by precond_multi_blocks
+  // (n x W); padding columns hold ordinary finite values (1).  A block product reads rx / ry only.
+  const real *rx = nullptr, *ry = nullptr, *Minv = nullptr;
+  // every column its own values of A (CSR order), A' (CSC order) and the symmetric P, value blocks of nnz x W (MultiWork::vA ...);
+  // vP and vPdiag with P only; Minv is then built by precond_multi_blocks from vAt and vPdiag
+  const real *vA = nullptr, *vAt = nullptr, *vP = nullptr, *vPdiag = nullptr;
+
+  bool percol() const { return rx != nullptr; } // the per-column instantiations: the workspace's rx, ry, M are not read
+  bool vcol() const { return vA != nullptr; }   // the per-value instantiations: the workspace's A.val, At.val, P.val are not read
+  // the rule of a solve, stated once: R is all three or none; values are all or none, vP / vPdiag exactly with P; values need R
+  void check(bool has_P) const {
+    if (percol() != (ry != nullptr) || percol() != (Minv != nullptr)) throw HipError("scs_amd: per-column R needs rx, ry and Minv together");
+    if (vcol() != (vAt != nullptr) || (vcol() && has_P) != (vP != nullptr) || (vcol() && has_P) != (vPdiag != nullptr))
+      throw HipError("scs_amd: per-column values need vA, vAt and, with P, vP");
+    if (vcol() && !percol()) throw HipError("scs_amd: per-column values run under per-column R");
+  }
+  static MultiOp shared() { return MultiOp(); }
+  static MultiOp r_blocks(const real *rx, const real *ry, const real *Minv) {
+    MultiOp o;
+    o.rx = rx, o.ry = ry, o.Minv = Minv;
+    return o;
+  }
+  // the x and y rows of one l x W block [R_x rows | R_y rows | ...], as a family holds its R (nw = n W)
+  static MultiOp r_rows(const real *R, size_t nw, const real *Minv) { return r_blocks(R, R + nw, Minv); }
+  // the workspace's own R blocks and, with `values`, the value blocks of its last set call
+  static MultiOp of_work(const MultiWork &mw, bool values, bool has_P) {
+    MultiOp o = r_blocks(mw.rxb.p, mw.ryb.p, mw.Mb.p);
+    if (values) o.vA = mw.vA.p, o.vAt = mw.vAt.p, o.vP = has_P ? mw.vP.p : nullptr, o.vPdiag = has_P ? mw.vPdiag.p : nullptr;
+    return o;
+  }
+  // this op's values under the x and y rows of another R block (a block product under a caller's R): no preconditioner goes
+  // with that R, so Minv is null and the result serves products only -- check() refuses it for a solve
+  MultiOp with_r_rows(const real *R, size_t nw) const {
+    MultiOp o = *this;
+    o.rx = R, o.ry = R + nw, o.Minv = nullptr;
+    return o;
+  }
+};
+
 // What a block solve works on when the caller holds the blocks (LinSys::solve_multi_blocks), all in device memory, in the layout
 // of spmm.h.  warm_part != null: the tolerance of column k is formed on the device, as solve_dev forms it, as
 //     max(1e-12, 0.2 * min(tolv[k], max(column k of warm_part[0 .. warm_cnt)) * warm_scale))      (reference src/scs.c:745-762)
@@ -99,13 +142,9 @@ struct MultiRhs {
   // iterations of their own solves: scs_amd_solve_family_stream); passed to the kernel by value, not read after the call returns
   const real *warm_scale_col = nullptr;
   const int *pre_stopped = nullptr;
-  // every column under its own diag_r: R_x (n x W), R_y (m x W) and the preconditioner built from them by precond_multi_blocks
-  // (n x W); padding columns hold ordinary finite values (1).  All three or none; all null = the workspace's shared rx / ry / M.
-  const real *rx = nullptr, *ry = nullptr, *Minv = nullptr;
-  // every column its own values of A (CSR order), A' (CSC order) and the symmetric P, value blocks of nnz x W (MultiWork::vA ...);
-  // vP and vPdiag with P only; needs rx / ry / Minv (Minv built by precond_multi_blocks from vAt and vPdiag).  All null = the
-  // workspace's shared values.
-  const real *vA = nullptr, *vAt = nullptr, *vP = nullptr, *vPdiag = nullptr;
+  MultiOp op; // the system of every column; default: the workspace's shared R and values
+  MultiRhs() = default;
+  MultiRhs(real *bx_, real *by_, const real *s_, const MultiOp &op_) : bx(bx_), by(by_), s(s_), op(op_) {}
 };
 
 struct LinSys {
@@ -205,16 +244,13 @@ struct LinSys {
   // vals: the matrix's values per column, an nnz x W block in mat's entry order (null: mat's own, shared by the columns)
   void launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
                    bool dcol = false, const real *vals = nullptr);
-  // rxb / ryb (both or neither): R_x / R_y per column as blocks instead of the workspace's own; vA / vAt / vP: value blocks
-  void mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip = nullptr, const int *allskip = nullptr,
-                         const real *rxb = nullptr, const real *ryb = nullptr, const real *vA = nullptr, const real *vAt = nullptr,
-                         const real *vP = nullptr);
-  void precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv, const real *vAt = nullptr, const real *vPdiag = nullptr);
+  // Y = G X under op (its rx / ry and vA / vAt / vP; Minv is not read), skipping the columns of cskip / everything under allskip
+  void mat_vec_multi_dev(int W, const MultiOp &op, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip);
+  void precond_multi_blocks(int W, const MultiOp &op, real *Minv); // Minv from op's rx / ry and, with values, its vAt / vPdiag
   // value blocks of the per-value solves (MultiWork::vA ...; scs_amd_linsys_set_values_multi)
   void ensure_multi_values(int W);
   void set_multi_values(int K, int W, const real *AX, size_t ldax, const real *PX, size_t ldpx);
   void free_multi_values();
-  void solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out);
   void solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out);
   // ---- new values on the pattern given to init (scs_amd_linsys_update_values, include/scs_amd.h) ----
   // Position maps, device resident, built by the first update that needs them and freed with the workspace:

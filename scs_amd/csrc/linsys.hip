@@ -1727,6 +1727,57 @@ namespace scsamd {
 int selected_device() { return t_device >= 0 ? t_device : g_default_device.load(std::memory_order_relaxed); }
 }
 
+// The frame of every entry below that runs device work: the device made current, the body, and a failure (a HipError or any other
+// exception) printed and turned into -1.  sync != null: that stream is waited on after a failure, so that nothing of the call is
+// still reading or writing the caller's arrays when the entry returns.
+template <typename F>
+static scs_int guarded(int device, const hipStream_t *sync, F &&body) {
+  try {
+    HIP_CHECK(hipSetDevice(device));
+    body();
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    if (sync) (void)hipStreamSynchronize(*sync);
+    return -1;
+  }
+  return 0;
+}
+enum OnFailure { LEAVE_STREAM, SYNC_STREAM };
+template <typename F>
+static scs_int guarded(ScsLinSysWork *w, OnFailure f, F &&body) {
+  return guarded(w->device, f == SYNC_STREAM ? &w->ls.stream : nullptr, body);
+}
+// an entry on device pointers: fn(x, y) under the frame, then the poll for a launch error
+template <typename F>
+static scs_int with_work(ScsLinSysWork *w, const void *a, const void *b, F &&fn) {
+  if (!w || !a || !b) return -1;
+  return guarded(w, LEAVE_STREAM, [&] {
+    fn(static_cast<const real *>(a), static_cast<real *>(const_cast<void *>(b)));
+    HIP_CHECK(hipGetLastError());
+  });
+}
+// the same on blocks in the device layout of spmm.h: fn at the layout width W of nrhs columns, fn1 for one column
+template <typename F, typename F1>
+static scs_int with_work_multi(ScsLinSysWork *w, scs_int nrhs, const void *a, const void *b, F &&fn, F1 &&fn1) {
+  const int W = multi_width((long long)nrhs);
+  if (!w || !a || !b || W == 0) return -1;
+  if (W == 1) return with_work(w, a, b, fn1);
+  return with_work(w, a, b, [&](const real *x, real *y) {
+    w->ls.ensure_multi(W);
+    fn(W, x, y);
+  });
+}
+static scs_int refuse(const char *what) {
+  fprintf(stderr, "scs_amd: %s\n", what);
+  return -1;
+}
+// every value finite?  (the one host pass over the entries an update makes)
+static bool all_finite(const scs_float *v, long long len) {
+  for (long long k = 0; k < len; ++k)
+    if (!std::isfinite((double)v[k])) return false;
+  return true;
+}
+
 extern "C" {
 
 scs_int scs_amd_device_count(void) {
@@ -1787,9 +1838,8 @@ const char *scs_get_lin_sys_method(void) { return "sparse-indirect-pcg-hip-gfx95
 ScsLinSysWork *scs_init_lin_sys_work(const ScsMatrix *A, const ScsMatrix *P, const scs_float *diag_r) {
   if (!A || !diag_r) return nullptr;
   ScsLinSysWork *w = nullptr;
-  try {
-    const int dev = selected_device(); // snapshot once: another thread may re-select concurrently
-    HIP_CHECK(hipSetDevice(dev));
+  const int dev = selected_device(); // snapshot once: another thread may re-select concurrently
+  const scs_int rc = guarded(dev, nullptr, [&] {
     if (!fits_int32(A) || !fits_int32(P)) throw HipError("scs_amd: matrix sizes / nonzero count exceed 32-bit device indexing");
     w = new ScsLinSysWork();
     w->device = dev;
@@ -1801,8 +1851,8 @@ ScsLinSysWork *scs_init_lin_sys_work(const ScsMatrix *A, const ScsMatrix *P, con
     w->ls.s_stage.alloc((size_t)A->n);
     w->ls.set_diag_r_host(diag_r);
     HIP_CHECK(hipStreamSynchronize(w->ls.stream));
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
+  });
+  if (rc != 0) {
     delete w;
     return nullptr;
   }
@@ -1826,146 +1876,42 @@ scs_int scs_solve_lin_sys(ScsLinSysWork *w, scs_float *b, const scs_float *s, sc
     // same diagnostic as private.c:288-292: caller was not built with -DINDIRECT=1
     printf("Warning: tol = %4f <= 0, likely compiled without setting INDIRECT flag.\n", (double)tol);
   }
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    solve_one_host(w->ls, b, s, tol);
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    return -1;
-  }
-  return 0;
+  return guarded(w, LEAVE_STREAM, [&] { solve_one_host(w->ls, b, s, tol); });
 }
 
 // ---- blocks of right-hand sides: K solves of scs_solve_lin_sys (private.c:284-324) on one workspace ----
 scs_int scs_amd_linsys_multi_width(scs_int nrhs) { return (scs_int)multi_width((long long)nrhs); }
 
-// the block solves of the host-pointer boundary.  DR == null: the columns share the workspace's diag_r
-// (scs_amd_solve_lin_sys_multi); else column k runs under column k of DR (scs_amd_solve_lin_sys_multi_r).
-static scs_int solve_multi_host(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
-                                const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
-  LinSys &ls = w->ls;
-  const size_t n = ls.n, m = ls.m, sz = sizeof(real);
-  if ((long long)ldb < (long long)(n + m) || (S && (long long)lds < (long long)n)) return -1;
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    if (ls.shard) throw HipError("scs_amd: block solves are not available on a row-sharded workspace");
-    for (scs_int c0 = 0; c0 < nrhs; c0 += MULTI_W_MAX) { // chunks of at most 16 columns
-      const int K = (int)std::min<scs_int>(MULTI_W_MAX, nrhs - c0);
-      scs_float *Bc = B + (size_t)c0 * (size_t)ldb;
-      const scs_float *Sc = S ? S + (size_t)c0 * (size_t)lds : nullptr;
-      if (K == 1 && !DR) { // the single-vector path, bit for bit
-        const int its = solve_one_host(ls, Bc, Sc, tol[c0]);
-        if (iters) iters[c0] = its;
-        continue;
-      }
-      const int W = K == 1 ? 2 : multi_width(K); // one column under its own R: a block of width 2, off the single-vector state
-      if (DR)
-        ls.ensure_multi_r(W);
-      else
-        ls.ensure_multi(W);
-      MultiWork &mw = *ls.multi;
-      const int g = ls.vec_grid((long long)(n + m));
-      if (DR) { // staged column-major in gt (B comes after it, in stream order); padding columns 1; then the preconditioner
-        HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, DR + (size_t)c0 * (size_t)lddr, (size_t)lddr * sz, (n + m) * sz, (size_t)K,
-                                   hipMemcpyHostToDevice, ls.stream));
-        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.rxb.p, (int)n,
-                                             mw.ryb.p, (int)m, K, (real)1));
-        ls.precond_multi_blocks(W, mw.rxb.p, mw.ryb.p, mw.Mb.p);
-      }
-      if (Sc) { // staged column-major in z, transposed into s on the device
-        HIP_CHECK(hipMemcpy2DAsync(mw.z.p, n * sz, Sc, (size_t)lds * sz, n * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
-        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.z.p, mw.s.p, (int)n,
-                                             (real *)nullptr, 0, K, (real)0));
-      }
-      HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, Bc, (size_t)ldb * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
-                                           (int)m, K, (real)0));
-      int its[MULTI_W_MAX];
-      if (DR) {
-        MultiRhs a;
-        a.bx = mw.bx.p;
-        a.by = mw.by.p;
-        a.s = Sc ? mw.s.p : nullptr;
-        a.rx = mw.rxb.p;
-        a.ry = mw.ryb.p;
-        a.Minv = mw.Mb.p;
-        ls.solve_multi_blocks(K, W, a, tol + c0, its);
-      } else {
-        ls.solve_multi_dev(K, W, Sc != nullptr, tol + c0, its);
-      }
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
-                                           (int)m, K));
-      HIP_CHECK(hipMemcpy2DAsync(Bc, (size_t)ldb * sz, mw.gt.p, (n + m) * sz, (n + m) * sz, (size_t)K, hipMemcpyDeviceToHost, ls.stream));
-      HIP_CHECK(hipStreamSynchronize(ls.stream));
-      HIP_CHECK(hipGetLastError());
-      if (iters)
-        for (int k = 0; k < K; ++k) iters[c0 + k] = its[k];
-    }
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(ls.stream); // nothing of this call may still be reading or writing the caller's block
-    return -1;
-  }
-  return 0;
-}
+// ---- the host boundary of the three block solves: scs_amd_solve_lin_sys_multi, _multi_r (DR) and _multi_v (own values) ----
+// layout width of a block of nrhs columns.  own_state: the block brings its own R or values -- then one column runs at width 2,
+// off the single-vector state
+static int block_width(scs_int nrhs, bool own_state) { return nrhs == 1 && own_state ? 2 : multi_width((long long)nrhs); }
 
-scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B, scs_int ldb, const scs_float *S, scs_int lds,
-                                    const scs_float *tol, scs_int *iters) {
-  if (!w || !B || !tol || nrhs < 1) return -1;
-  return solve_multi_host(w, nrhs, nullptr, 0, B, ldb, S, lds, tol, iters);
-}
-
-// every column under its own diag_r (include/scs_amd.h); the checks come before any device call
-scs_int scs_amd_solve_lin_sys_multi_r(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
-                                      const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
-  if (!w || !DR || !B || !tol || nrhs < 1) return -1;
-  const long long len = (long long)w->ls.n + w->ls.m;
-  if (w->ls.shard || (long long)lddr < len || (long long)ldb < len) return -1;
+// every entry of the nrhs columns of DR (len each, leading dimension lddr) finite and positive?
+static bool diag_r_block_ok(const scs_float *DR, scs_int lddr, long long len, scs_int nrhs) {
   for (scs_int k = 0; k < nrhs; ++k) {
     const scs_float *d = DR + (size_t)k * (size_t)lddr;
     for (long long i = 0; i < len; ++i)
-      if (!(std::isfinite((double)d[i]) && d[i] > 0)) return -1;
+      if (!(std::isfinite((double)d[i]) && d[i] > 0)) return false;
   }
-  return solve_multi_host(w, nrhs, DR, lddr, B, ldb, S, lds, tol, iters);
+  return true;
 }
 
-// ---- K systems on the workspace's pattern, every column its own values of A and P (include/scs_amd.h) ----
-static bool all_finite(const scs_float *v, long long len);
-static scs_int refuse(const char *what) {
-  fprintf(stderr, "scs_amd: %s\n", what);
-  return -1;
+// K columns of a column-major host block (nx + ny each, leading dimension ld) into the block layout: copied column-major into
+// `stage`, then transposed into dx (nx x W) and dy (ny x W; null with ny = 0) on the device; padding columns become `fill`
+static void stage_block(LinSys &ls, int W, int K, const scs_float *src, size_t ld, real *stage, real *dx, size_t nx, real *dy, size_t ny,
+                        real fill) {
+  const size_t len = (nx + ny) * sizeof(real);
+  HIP_CHECK(hipMemcpy2DAsync(stage, len, src, ld * sizeof(real), len, (size_t)K, hipMemcpyHostToDevice, ls.stream));
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(ls.vec_grid((long long)ls.n + ls.m)), dim3(SCSAMD_BLOCK), 0, ls.stream, stage, dx,
+                                       (int)nx, dy, (int)ny, K, fill));
 }
-// layout width of a per-value block of nrhs columns: one column runs at width 2, off the single-vector state
-static int values_width(scs_int nrhs) { return nrhs == 1 ? 2 : multi_width((long long)nrhs); }
-
-// the checks come before any device call; a refused call leaves the stored blocks as they were
-scs_int scs_amd_linsys_set_values_multi(ScsLinSysWork *w, scs_int nrhs, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
-  if (!w || !AX) return refuse("set_values_multi: w and AX must be given");
-  LinSys &ls = w->ls;
-  if (ls.shard) return refuse("set_values_multi: a row-sharded workspace takes no values per column");
-  if ((PX != nullptr) != ls.has_P) return refuse("set_values_multi: PX must be given exactly when the workspace has a P");
-  if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("set_values_multi: nrhs must be 1 .. 16 (set and solve in groups)");
-  const long long nza = ls.At.nnz, nzp = ls.has_P ? ls.nnzP_up : 0;
-  if ((long long)ldax < nza || (PX && (long long)ldpx < nzp)) return refuse("set_values_multi: a leading dimension is shorter than its column");
-  for (scs_int k = 0; k < nrhs; ++k)
-    if (!all_finite(AX + (size_t)k * (size_t)ldax, nza) || (PX && !all_finite(PX + (size_t)k * (size_t)ldpx, nzp)))
-      return refuse("set_values_multi: a matrix value is not finite");
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    ls.set_multi_values((int)nrhs, values_width(nrhs), AX, (size_t)ldax, PX, (size_t)ldpx);
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(ls.stream);
-    return -1;
-  }
-  return 0;
-}
-
-void scs_amd_linsys_free_values_multi(ScsLinSysWork *w) {
-  if (!w) return;
-  (void)hipSetDevice(w->device);
-  (void)hipStreamSynchronize(w->ls.stream);
-  w->ls.free_multi_values();
+// and back: K columns of [sx (n x W); sy (m x W)] through `stage` into the caller's block
+static void unstage_block(LinSys &ls, int W, int K, scs_float *dst, size_t ld, real *stage, const real *sx, const real *sy) {
+  const size_t len = ((size_t)ls.n + ls.m) * sizeof(real);
+  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_from_block<MW>, dim3(ls.vec_grid((long long)ls.n + ls.m)), dim3(SCSAMD_BLOCK), 0, ls.stream, stage, sx,
+                                       ls.n, sy, ls.m, K));
+  HIP_CHECK(hipMemcpy2DAsync(dst, ld * sizeof(real), stage, len, len, (size_t)K, hipMemcpyDeviceToHost, ls.stream));
 }
 
 // the workspace's diag_r in every column of its R blocks at width W (a per-value call without an R of its own)
@@ -1978,6 +1924,96 @@ static void workspace_r_into_blocks(LinSys &ls, int W) {
                                        (const real *)ls.ry.p, mw.ryb.p, m));
 }
 
+// One chunk of K <= 16 columns: stage, solve, bring back; returns with the stream idle.  DR (or null): column k under column k of
+// DR.  own_values: column k with the values of the last set call, under DR or else the workspace's diag_r replicated into the R
+// blocks.  Neither: the columns share the workspace's R and values, and one column is the single-vector path, bit for bit.
+// Staging: DR, then B, column-major in gt (in stream order; gt holds Gp and tmp during the solve), S in z.
+static void solve_chunk_host(LinSys &ls, int K, bool own_values, const scs_float *DR, size_t lddr, scs_float *B, size_t ldb, const scs_float *S,
+                             size_t lds, const scs_float *tol, scs_int *iters) {
+  const bool own_r = DR || own_values;
+  if (K == 1 && !own_r) {
+    const int its = solve_one_host(ls, B, S, tol[0]);
+    if (iters) iters[0] = its;
+    return;
+  }
+  const int W = block_width(K, own_r);
+  if (own_r)
+    ls.ensure_multi_r(W);
+  else
+    ls.ensure_multi(W);
+  MultiWork &mw = *ls.multi;
+  const size_t n = ls.n, m = ls.m;
+  const MultiOp op = own_r ? MultiOp::of_work(mw, own_values, ls.has_P) : MultiOp::shared();
+  if (own_r) { // the R of every column (padding columns 1), then every column's preconditioner, from its own values if it has them
+    if (DR)
+      stage_block(ls, W, K, DR, lddr, mw.gt.p, mw.rxb.p, n, mw.ryb.p, m, (real)1);
+    else
+      workspace_r_into_blocks(ls, W);
+    ls.precond_multi_blocks(W, op, mw.Mb.p);
+  }
+  if (S) stage_block(ls, W, K, S, lds, mw.z.p, mw.s.p, n, nullptr, 0, (real)0);
+  stage_block(ls, W, K, B, ldb, mw.gt.p, mw.bx.p, n, mw.by.p, m, (real)0);
+  int its[MULTI_W_MAX];
+  ls.solve_multi_blocks(K, W, MultiRhs(mw.bx.p, mw.by.p, S ? mw.s.p : nullptr, op), tol, its);
+  unstage_block(ls, W, K, B, ldb, mw.gt.p, mw.bx.p, mw.by.p);
+  HIP_CHECK(hipStreamSynchronize(ls.stream));
+  HIP_CHECK(hipGetLastError());
+  if (iters)
+    for (int k = 0; k < K; ++k) iters[k] = its[k];
+}
+
+// nrhs columns in chunks of at most 16.  A failure leaves nothing of this call reading or writing the caller's blocks.
+static scs_int solve_multi_host(ScsLinSysWork *w, scs_int nrhs, bool own_values, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
+                                const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
+  LinSys &ls = w->ls;
+  if ((long long)ldb < (long long)ls.n + ls.m || (S && (long long)lds < (long long)ls.n)) return -1;
+  return guarded(w, SYNC_STREAM, [&] {
+    if (ls.shard) throw HipError("scs_amd: block solves are not available on a row-sharded workspace");
+    for (scs_int c0 = 0; c0 < nrhs; c0 += MULTI_W_MAX)
+      solve_chunk_host(ls, (int)std::min<scs_int>(MULTI_W_MAX, nrhs - c0), own_values, DR ? DR + (size_t)c0 * (size_t)lddr : nullptr,
+                       (size_t)lddr, B + (size_t)c0 * (size_t)ldb, (size_t)ldb, S ? S + (size_t)c0 * (size_t)lds : nullptr, (size_t)lds, tol + c0,
+                       iters ? iters + c0 : nullptr);
+  });
+}
+
+scs_int scs_amd_solve_lin_sys_multi(ScsLinSysWork *w, scs_int nrhs, scs_float *B, scs_int ldb, const scs_float *S, scs_int lds,
+                                    const scs_float *tol, scs_int *iters) {
+  if (!w || !B || !tol || nrhs < 1) return -1;
+  return solve_multi_host(w, nrhs, false, nullptr, 0, B, ldb, S, lds, tol, iters);
+}
+
+// every column under its own diag_r (include/scs_amd.h); the checks come before any device call
+scs_int scs_amd_solve_lin_sys_multi_r(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
+                                      const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
+  if (!w || !DR || !B || !tol || nrhs < 1) return -1;
+  const long long len = (long long)w->ls.n + w->ls.m;
+  if (w->ls.shard || (long long)lddr < len || (long long)ldb < len || !diag_r_block_ok(DR, lddr, len, nrhs)) return -1;
+  return solve_multi_host(w, nrhs, false, DR, lddr, B, ldb, S, lds, tol, iters);
+}
+
+// ---- K systems on the workspace's pattern, every column its own values of A and P (include/scs_amd.h) ----
+// the checks come before any device call; a refused call leaves the stored blocks as they were
+scs_int scs_amd_linsys_set_values_multi(ScsLinSysWork *w, scs_int nrhs, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+  if (!w || !AX) return refuse("set_values_multi: w and AX must be given");
+  LinSys &ls = w->ls;
+  if (ls.shard) return refuse("set_values_multi: a row-sharded workspace takes no values per column");
+  if ((PX != nullptr) != ls.has_P) return refuse("set_values_multi: PX must be given exactly when the workspace has a P");
+  if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("set_values_multi: nrhs must be 1 .. 16 (set and solve in groups)");
+  const long long nza = ls.At.nnz, nzp = ls.has_P ? ls.nnzP_up : 0;
+  if ((long long)ldax < nza || (PX && (long long)ldpx < nzp)) return refuse("set_values_multi: a leading dimension is shorter than its column");
+  for (scs_int k = 0; k < nrhs; ++k)
+    if (!all_finite(AX + (size_t)k * (size_t)ldax, nza) || (PX && !all_finite(PX + (size_t)k * (size_t)ldpx, nzp)))
+      return refuse("set_values_multi: a matrix value is not finite");
+  return guarded(w, SYNC_STREAM, [&] { ls.set_multi_values((int)nrhs, block_width(nrhs, true), AX, (size_t)ldax, PX, (size_t)ldpx); });
+}
+
+void scs_amd_linsys_free_values_multi(ScsLinSysWork *w) {
+  if (!w) return;
+  (void)hipSetDevice(w->device);
+  (void)hipStreamSynchronize(w->ls.stream);
+  w->ls.free_multi_values();
+}
+
 scs_int scs_amd_solve_lin_sys_multi_v(ScsLinSysWork *w, scs_int nrhs, const scs_float *DR, scs_int lddr, scs_float *B, scs_int ldb,
                                       const scs_float *S, scs_int lds, const scs_float *tol, scs_int *iters) {
   if (!w || !B || !tol) return refuse("solve_lin_sys_multi_v: w, B and tol must be given");
@@ -1986,99 +2022,26 @@ scs_int scs_amd_solve_lin_sys_multi_v(ScsLinSysWork *w, scs_int nrhs, const scs_
   if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("solve_lin_sys_multi_v: nrhs must be 1 .. 16 (set and solve in groups)");
   if (!ls.multi || ls.multi->vcols == 0) return refuse("solve_lin_sys_multi_v: no values are set (scs_amd_linsys_set_values_multi)");
   if (ls.multi->vcols != (int)nrhs) return refuse("solve_lin_sys_multi_v: nrhs differs from the set call's");
-  const size_t n = ls.n, m = ls.m, sz = sizeof(real);
-  const long long len = (long long)(n + m);
-  if ((long long)ldb < len || (S && (long long)lds < (long long)n) || (DR && (long long)lddr < len))
+  const long long len = (long long)ls.n + ls.m;
+  if ((long long)ldb < len || (S && (long long)lds < (long long)ls.n) || (DR && (long long)lddr < len))
     return refuse("solve_lin_sys_multi_v: a leading dimension is shorter than its column");
-  if (DR)
-    for (scs_int k = 0; k < nrhs; ++k) {
-      const scs_float *d = DR + (size_t)k * (size_t)lddr;
-      for (long long i = 0; i < len; ++i)
-        if (!(std::isfinite((double)d[i]) && d[i] > 0)) return refuse("solve_lin_sys_multi_v: diag_r must be finite and positive");
-    }
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    const int K = (int)nrhs, W = values_width(nrhs);
-    ls.ensure_multi_r(W);
-    MultiWork &mw = *ls.multi;
-    const int g = ls.vec_grid(len);
-    if (DR) { // staged column-major in gt (B comes after it, in stream order); padding columns 1
-      HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, DR, (size_t)lddr * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.rxb.p, (int)n, mw.ryb.p,
-                                           (int)m, K, (real)1));
-    } else {
-      workspace_r_into_blocks(ls, W);
-    }
-    ls.precond_multi_blocks(W, mw.rxb.p, mw.ryb.p, mw.Mb.p, mw.vAt.p, mw.vPdiag.p); // every column's, from its own values
-    if (S) { // staged column-major in z, transposed into s on the device
-      HIP_CHECK(hipMemcpy2DAsync(mw.z.p, n * sz, S, (size_t)lds * sz, n * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.z.p, mw.s.p, (int)n,
-                                           (real *)nullptr, 0, K, (real)0));
-    }
-    HIP_CHECK(hipMemcpy2DAsync(mw.gt.p, (n + m) * sz, B, (size_t)ldb * sz, (n + m) * sz, (size_t)K, hipMemcpyHostToDevice, ls.stream));
-    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_to_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
-                                         (int)m, K, (real)0));
-    MultiRhs a;
-    a.bx = mw.bx.p;
-    a.by = mw.by.p;
-    a.s = S ? mw.s.p : nullptr;
-    a.rx = mw.rxb.p;
-    a.ry = mw.ryb.p;
-    a.Minv = mw.Mb.p;
-    a.vA = mw.vA.p;
-    a.vAt = mw.vAt.p;
-    a.vP = ls.has_P ? mw.vP.p : nullptr;
-    a.vPdiag = ls.has_P ? mw.vPdiag.p : nullptr;
-    int its[MULTI_W_MAX];
-    ls.solve_multi_blocks(K, W, a, tol, its);
-    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_from_block<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, mw.gt.p, mw.bx.p, (int)n, mw.by.p,
-                                         (int)m, K));
-    HIP_CHECK(hipMemcpy2DAsync(B, (size_t)ldb * sz, mw.gt.p, (n + m) * sz, (n + m) * sz, (size_t)K, hipMemcpyDeviceToHost, ls.stream));
-    HIP_CHECK(hipStreamSynchronize(ls.stream));
-    HIP_CHECK(hipGetLastError());
-    if (iters)
-      for (int k = 0; k < K; ++k) iters[k] = its[k];
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(ls.stream); // nothing of this call may still be reading or writing the caller's block
-    return -1;
-  }
-  return 0;
+  if (DR && !diag_r_block_ok(DR, lddr, len, nrhs)) return refuse("solve_lin_sys_multi_v: diag_r must be finite and positive");
+  return solve_multi_host(w, nrhs, true, DR, lddr, B, ldb, S, lds, tol, iters);
 }
 
 scs_int scs_update_lin_sys_diag_r(ScsLinSysWork *w, const scs_float *new_diag_r) {
   if (!w || !new_diag_r) return -1;
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
+  return guarded(w, LEAVE_STREAM, [&] {
     w->ls.set_diag_r_host(new_diag_r);
     HIP_CHECK(hipStreamSynchronize(w->ls.stream));
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    return -1;
-  }
-  return 0;
-}
-
-// every value finite?  (the one host pass over the entries an update makes)
-static bool all_finite(const scs_float *v, long long len) {
-  for (long long k = 0; k < len; ++k)
-    if (!std::isfinite((double)v[k])) return false;
-  return true;
+  });
 }
 
 scs_int scs_amd_linsys_update_values(ScsLinSysWork *w, const scs_float *Ax, const scs_float *Px) {
   if (!w || w->ls.shard || (Px && !w->ls.has_P)) return -1;
   if ((Ax && !all_finite(Ax, w->ls.At.nnz)) || (Px && !all_finite(Px, w->ls.nnzP_up))) return -1;
   if (!Ax && !Px) return 0;
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    w->ls.update_values(Ax, Px);
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(w->ls.stream);
-    return -1;
-  }
-  return 0;
+  return guarded(w, SYNC_STREAM, [&] { w->ls.update_values(Ax, Px); });
 }
 
 void scs_free_lin_sys_work(ScsLinSysWork *w) {
@@ -2088,77 +2051,44 @@ void scs_free_lin_sys_work(ScsLinSysWork *w) {
 }
 
 // operator pieces on device pointers (row-sharded systems, scs_amd/shard.py)
-static scs_int with_work(ScsLinSysWork *w, const void *a, const void *b, void (*fn)(LinSys &, const real *, real *)) {
-  if (!w || !a || !b) return -1;
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    fn(w->ls, static_cast<const real *>(a), static_cast<real *>(const_cast<void *>(b)));
-    HIP_CHECK(hipGetLastError());
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    return -1;
-  }
-  return 0;
-}
 scs_int scs_amd_linsys_mat_vec_dev(ScsLinSysWork *w, const scs_float *x_dev, scs_float *y_dev) {
-  return with_work(w, x_dev, y_dev, [](LinSys &ls, const real *x, real *y) { ls.mat_vec_dev(x, y, nullptr); });
+  return with_work(w, x_dev, y_dev, [&](const real *x, real *y) { w->ls.mat_vec_dev(x, y, nullptr); });
 }
 scs_int scs_amd_linsys_mul_a_dev(ScsLinSysWork *w, const scs_float *x_dev, scs_float *y_dev) {
-  return with_work(w, x_dev, y_dev, [](LinSys &ls, const real *x, real *y) { ls.mul_A(x, y); });
+  return with_work(w, x_dev, y_dev, [&](const real *x, real *y) { w->ls.mul_A(x, y); });
 }
 scs_int scs_amd_linsys_mul_at_dev(ScsLinSysWork *w, const scs_float *y_dev, scs_float *x_dev) {
-  return with_work(w, y_dev, x_dev, [](LinSys &ls, const real *y, real *x) { ls.mul_At(y, x); });
+  return with_work(w, y_dev, x_dev, [&](const real *y, real *x) { w->ls.mul_At(y, x); });
 }
 // the same pieces on blocks in the device layout of spmm.h
-static scs_int with_work_multi(ScsLinSysWork *w, scs_int nrhs, const void *a, const void *b, void (*fn)(LinSys &, int, const real *, real *),
-                               void (*fn1)(LinSys &, const real *, real *)) {
-  if (!w || !a || !b) return -1;
-  const int W = multi_width((long long)nrhs);
-  if (W == 0) return -1;
-  if (W == 1) return with_work(w, a, b, fn1);
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    w->ls.ensure_multi(W);
-    fn(w->ls, W, static_cast<const real *>(a), static_cast<real *>(const_cast<void *>(b)));
-    HIP_CHECK(hipGetLastError());
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    return -1;
-  }
-  return 0;
-}
 scs_int scs_amd_linsys_mat_vec_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev) {
-  return with_work_multi(w, nrhs, X_dev, Y_dev, [](LinSys &ls, int W, const real *x, real *y) { ls.mat_vec_multi_dev(W, x, y, nullptr); },
-                         [](LinSys &ls, const real *x, real *y) { ls.mat_vec_dev(x, y, nullptr); });
+  return with_work_multi(
+      w, nrhs, X_dev, Y_dev, [&](int W, const real *x, real *y) { w->ls.mat_vec_multi_dev(W, MultiOp::shared(), x, y, nullptr, nullptr, nullptr); },
+      [&](const real *x, real *y) { w->ls.mat_vec_dev(x, y, nullptr); });
 }
+static const EpiArgs no_epilogue{nullptr, nullptr, nullptr, nullptr};
 scs_int scs_amd_linsys_mul_a_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *X_dev, scs_float *Y_dev) {
-  return with_work_multi(w, nrhs, X_dev, Y_dev, [](LinSys &ls, int W, const real *x, real *y) {
-    EpiArgs e{nullptr, nullptr, nullptr, nullptr};
-    ls.launch_spmm(W, EPI_PLAIN, ls.A, x, y, e, nullptr, nullptr); }, [](LinSys &ls, const real *x, real *y) { ls.mul_A(x, y); });
+  return with_work_multi(
+      w, nrhs, X_dev, Y_dev, [&](int W, const real *x, real *y) { w->ls.launch_spmm(W, EPI_PLAIN, w->ls.A, x, y, no_epilogue, nullptr, nullptr); },
+      [&](const real *x, real *y) { w->ls.mul_A(x, y); });
 }
 scs_int scs_amd_linsys_mul_at_multi_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *Y_dev, scs_float *X_dev) {
-  return with_work_multi(w, nrhs, Y_dev, X_dev, [](LinSys &ls, int W, const real *y, real *x) {
-    EpiArgs e{nullptr, nullptr, nullptr, nullptr};
-    ls.launch_spmm(W, EPI_PLAIN, ls.At, y, x, e, nullptr, nullptr); }, [](LinSys &ls, const real *y, real *x) { ls.mul_At(y, x); });
+  return with_work_multi(
+      w, nrhs, Y_dev, X_dev, [&](int W, const real *y, real *x) { w->ls.launch_spmm(W, EPI_PLAIN, w->ls.At, y, x, no_epilogue, nullptr, nullptr); },
+      [&](const real *y, real *x) { w->ls.mul_At(y, x); });
 }
 // G X with R_x / R_y per column: R_dev = [R_x (n x W); R_y (m x W)] in the block layout; one column runs at width 2
 scs_int scs_amd_linsys_mat_vec_multi_r_dev(ScsLinSysWork *w, scs_int nrhs, const scs_float *R_dev, const scs_float *X_dev,
                                            scs_float *Y_dev) {
   if (!w || !R_dev || !X_dev || !Y_dev) return -1;
   if (nrhs < 1 || nrhs > MULTI_W_MAX || w->ls.shard) return -1;
-  const int W = nrhs == 1 ? 2 : multi_width((long long)nrhs);
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
+  return with_work(w, X_dev, Y_dev, [&](const real *x, real *y) {
     LinSys &ls = w->ls;
+    const int W = block_width(nrhs, true);
     ls.ensure_multi(W);
     const real *R = static_cast<const real *>(R_dev);
-    ls.mat_vec_multi_dev(W, static_cast<const real *>(X_dev), static_cast<real *>(Y_dev), nullptr, nullptr, nullptr, R, R + (size_t)ls.n * W);
-    HIP_CHECK(hipGetLastError());
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    return -1;
-  }
-  return 0;
+    ls.mat_vec_multi_dev(W, MultiOp::r_rows(R, (size_t)ls.n * W, nullptr), x, y, nullptr, nullptr, nullptr);
+  });
 }
 // G_k X(:,k) with the values of the last set call and R_x / R_y per column (R_dev as above; null: the workspace's diag_r in every
 // column, replicated into the workspace's R blocks)
@@ -2169,25 +2099,13 @@ scs_int scs_amd_linsys_mat_vec_multi_v_dev(ScsLinSysWork *w, scs_int nrhs, const
   if (nrhs < 1 || nrhs > MULTI_W_MAX) return refuse("mat_vec_multi_v_dev: nrhs must be 1 .. 16");
   if (!ls.multi || ls.multi->vcols == 0) return refuse("mat_vec_multi_v_dev: no values are set (scs_amd_linsys_set_values_multi)");
   if (ls.multi->vcols != (int)nrhs) return refuse("mat_vec_multi_v_dev: nrhs differs from the set call's");
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    const int W = values_width(nrhs);
+  return with_work(w, X_dev, Y_dev, [&](const real *x, real *y) {
+    const int W = block_width(nrhs, true);
     ls.ensure_multi_r(W);
-    MultiWork &mw = *ls.multi;
-    const real *rxb = static_cast<const real *>(R_dev), *ryb = rxb ? rxb + (size_t)ls.n * W : nullptr;
-    if (!rxb) {
-      workspace_r_into_blocks(ls, W);
-      rxb = mw.rxb.p;
-      ryb = mw.ryb.p;
-    }
-    ls.mat_vec_multi_dev(W, static_cast<const real *>(X_dev), static_cast<real *>(Y_dev), nullptr, nullptr, nullptr, rxb, ryb, mw.vA.p,
-                         mw.vAt.p, ls.has_P ? mw.vP.p : nullptr);
-    HIP_CHECK(hipGetLastError());
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    return -1;
-  }
-  return 0;
+    const MultiOp own = MultiOp::of_work(*ls.multi, true, ls.has_P);
+    if (!R_dev) workspace_r_into_blocks(ls, W);
+    ls.mat_vec_multi_dev(W, R_dev ? own.with_r_rows(static_cast<const real *>(R_dev), (size_t)ls.n * W) : own, x, y, nullptr, nullptr, nullptr);
+  });
 }
 // the SpMV kernel the workspace runs for A (which = 0) / A' (which = 1): the strings of scs_amd_get_spmv_kernel_name
 scs_int scs_amd_linsys_spmv_kernel_name(const ScsLinSysWork *w, scs_int which, char *buf, scs_int cap) {

@@ -15,19 +15,26 @@
 // Buffers (MultiWork, linsys.h): 7 n W + 2 m W values at the largest width used (6 n W + 2 m W without P), allocated at the
 // first block call, reused, freed with the workspace.
 //
-// Per-column R (MultiRhs::rx / ry / Minv): column k runs under its own diag_r_k = [R_x,k; R_y,k] and its own Jacobi preconditioner
+// What differs from column to column is one value, MultiOp (linsys.h), which MultiRhs carries and mat_vec_multi_dev,
+// precond_multi_blocks and solve_multi_blocks take; MultiOp::check states once which of its fields go together.
+//
+// Per-column R (MultiOp::rx / ry / Minv): column k runs under its own diag_r_k = [R_x,k; R_y,k] and its own Jacobi preconditioner
 // (k_m_precond), i.e. it computes what scs_update_lin_sys_diag_r(diag_r_k) followed by the single solve computes.  R_x, R_y and
 // M^-1 are then blocks in the block layout and the kernels that read them run in their per-column instantiation (the DCOL form of
 // csr_block_kernel, PERCOL of k_m_rhs_prep / k_m_cg_init / k_m_cg_update); A and P are still read once per product for all
 // columns.  The workspace's own rx, ry, M, captured graph and single-vector state are neither read nor written.  Three more blocks
 // (2 n W + m W values), allocated at the first per-column call only.
 //
-// Per-column values (MultiRhs::vA / vAt / vP / vPdiag): K systems on one pattern, column k with its own values of A and P, i.e. it
+// Per-column values (MultiOp::vA / vAt / vP / vPdiag): K systems on one pattern, column k with its own values of A and P, i.e. it
 // computes what scs_amd_linsys_update_values(values k) followed by the per-column-R solve computes.  The values are blocks of
 // nnz x W in the block layout (the VCOL form of csr_block_kernel and k_m_precond, spmm.h); the row pointers and indices are the
 // workspace's and are read once per product for all columns.  Always under per-column R: a caller without an R of their own gets
 // the workspace's replicated into the R blocks.  The workspace's A.val, At.val, P.val, Pdiag, rx, ry, M, layouts, captured graph
 // and single-vector state are neither read for the columns nor written.  Allocated by the first set call only.
+//
+// Host side: the instantiation of each kernel is chosen in one place -- spmm_built and launch_spmm_epi for csr_block_kernel,
+// launch_rhs_prep / launch_cg_init / launch_cg_update for the vector kernels with a per-column form -- and solve_multi_blocks
+// reads as the algorithm.  The width switch is MULTI_DISPATCH (common.h).
 #pragma once
 
 namespace scsamd {
@@ -319,59 +326,59 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_m_cg_direction(real *p, const 
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-template <int W>
-static void launch_spmm_w(int epi, bool dcol, int g, hipStream_t st, const CsrView &v, const real *X, real *Y, const EpiArgs &e,
-                          const int *cskip, const int *allskip, const real *vals, eoff bias) {
-  if (vals) { // every column its own values: the five instantiations the per-value solve uses (per-column d where there is a d)
-    const ValBlk<true> vb{vals, bias};
-    if (dcol != (epi == EPI_DIV || epi == EPI_GP || epi == EPI_NEGDIV)) throw HipError("scs_amd: per-column values run under per-column R");
-    switch (epi) {
-    case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN, false, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
-    case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV, true, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
-    case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP, true, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
-    case EPI_ACC: hipLaunchKernelGGL((csr_block_kernel<W, EPI_ACC, false, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
-    case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV, true, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vb); break;
-    default: throw HipError("scs_amd: bad block-product epilogue");
-    }
-    return;
+// The instantiations of csr_block_kernel that are built, 13 per width: shared values take a shared d with every epilogue (5) and a
+// per-column d where the epilogue has a d (3); per-column values take a per-column d exactly where there is a d (5).  The launch
+// below names a kernel under this predicate only, so a combination outside it cannot be built by accident: it is refused at run time.
+constexpr bool epi_has_d(int epi) { return epi == EPI_DIV || epi == EPI_GP || epi == EPI_NEGDIV; }
+constexpr bool spmm_built(int epi, bool dcol, bool vcol) { return vcol ? dcol == epi_has_d(epi) : !dcol || epi_has_d(epi); }
+
+struct SpmmArgs {
+  int g;
+  hipStream_t st;
+  CsrView v;
+  const real *X;
+  real *Y;
+  EpiArgs e;
+  const int *cskip, *allskip;
+  const real *vals;
+  eoff bias;
+};
+template <bool VCOL>
+static ValBlk<VCOL> val_blk(const real *vals, eoff bias) {
+  if constexpr (VCOL) return ValBlk<true>{vals, bias};
+  else return ValBlk<false>{};
+}
+template <int W, int EPI, bool DCOL, bool VCOL>
+static void launch_spmm_as(const SpmmArgs &a) {
+  if constexpr (spmm_built(EPI, DCOL, VCOL)) {
+    hipLaunchKernelGGL((csr_block_kernel<W, EPI, DCOL, VCOL>), dim3(a.g), dim3(SCSAMD_BLOCK), 0, a.st, a.v, a.X, a.Y, a.e, a.cskip, a.allskip,
+                       val_blk<VCOL>(a.vals, a.bias));
+  } else {
+    throw HipError(VCOL ? "scs_amd: per-column values run under per-column R" : "scs_amd: this block-product epilogue has no per-column form");
   }
-  const ValBlk<false> vs{};
-  if (dcol) { // e.d is a block: the per-column instantiations (the epilogues that have a d)
-    switch (epi) {
-    case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-    case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-    case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-    default: throw HipError("scs_amd: this block-product epilogue has no per-column form");
-    }
-    return;
-  }
+}
+template <int W, bool DCOL, bool VCOL>
+static void launch_spmm_epi(int epi, const SpmmArgs &a) {
   switch (epi) {
-  case EPI_PLAIN: hipLaunchKernelGGL((csr_block_kernel<W, EPI_PLAIN>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-  case EPI_DIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_DIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-  case EPI_GP: hipLaunchKernelGGL((csr_block_kernel<W, EPI_GP>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-  case EPI_ACC: hipLaunchKernelGGL((csr_block_kernel<W, EPI_ACC>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
-  case EPI_NEGDIV: hipLaunchKernelGGL((csr_block_kernel<W, EPI_NEGDIV>), dim3(g), dim3(SCSAMD_BLOCK), 0, st, v, X, Y, e, cskip, allskip, vs); break;
+  case EPI_PLAIN: return launch_spmm_as<W, EPI_PLAIN, DCOL, VCOL>(a);
+  case EPI_DIV: return launch_spmm_as<W, EPI_DIV, DCOL, VCOL>(a);
+  case EPI_GP: return launch_spmm_as<W, EPI_GP, DCOL, VCOL>(a);
+  case EPI_ACC: return launch_spmm_as<W, EPI_ACC, DCOL, VCOL>(a);
+  case EPI_NEGDIV: return launch_spmm_as<W, EPI_NEGDIV, DCOL, VCOL>(a);
   default: throw HipError("scs_amd: bad block-product epilogue");
   }
 }
-
-#define MULTI_DISPATCH(W_, CALL)                                                                                       \
+// a runtime flag as the constant FLAG (the PERCOL / DCOL / VCOL template arguments)
+#define MULTI_FLAG(flag_, FLAG, CALL)                                                                                  \
   do {                                                                                                                 \
-    switch (W_) {                                                                                                      \
-    case 2: { constexpr int MW = 2; CALL; } break;                                                                     \
-    case 4: { constexpr int MW = 4; CALL; } break;                                                                     \
-    case 8: { constexpr int MW = 8; CALL; } break;                                                                     \
-    case 16: { constexpr int MW = 16; CALL; } break;                                                                   \
-    default: throw HipError("scs_amd: bad block width");                                                               \
-    }                                                                                                                  \
+    if (flag_) { constexpr bool FLAG = true; CALL; } else { constexpr bool FLAG = false; CALL; }                       \
   } while (0)
 
 void LinSys::launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
                          bool dcol, const real *vals) {
-  const int g = spmm_grid(mat.rows, W);
-  CsrView v = mat.view();
-  if (vals) v.val = nullptr; // the pattern only: the values are the block's
-  MULTI_DISPATCH(W, launch_spmm_w<MW>(epi, dcol, g, stream, v, X, Y, e, cskip, allskip, vals, (eoff)mat.bias));
+  SpmmArgs a{spmm_grid(mat.rows, W), stream, mat.view(), X, Y, e, cskip, allskip, vals, (eoff)mat.bias};
+  if (vals) a.v.val = nullptr; // the pattern only: the values are the block's
+  MULTI_DISPATCH(W, MULTI_FLAG(dcol, DCOL, MULTI_FLAG(vals != nullptr, VCOL, (launch_spmm_epi<MW, DCOL, VCOL>(epi, a)))));
   n_spmv++;
 }
 
@@ -487,59 +494,74 @@ void LinSys::set_multi_values(int K, int W, const real *AX, size_t ldax, const r
 
 // Minv(n x W) = the Jacobi preconditioner of every column under its own rx (n x W) / ry (m x W): k_precond per column.
 // vAt (with vPdiag when there is a P): every column under its own values too; the workspace's At.val and Pdiag are not read.
-void LinSys::precond_multi_blocks(int W, const real *rxb, const real *ryb, real *Minv, const real *vAt, const real *vPdiag) {
+void LinSys::precond_multi_blocks(int W, const MultiOp &op, real *Minv) {
   CsrView v = At.view();
+  if (op.vcol()) v.val = nullptr;
+  const real *pd = !has_P ? nullptr : op.vcol() ? op.vPdiag : Pdiag.p;
   const int g = vec_grid((long long)n * W);
-  if (vAt) {
-    v.val = nullptr;
-    const ValBlk<true> vb{vAt, (eoff)At.bias};
-    const real *pd = has_P ? vPdiag : nullptr;
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_precond<MW, true>), dim3(g), dim3(SCSAMD_BLOCK), 0, stream, v, rxb, ryb, pd, Minv, vb));
-    return;
-  }
-  const real *pd = has_P ? Pdiag.p : nullptr;
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_precond<MW>, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, v, rxb, ryb, pd, Minv, ValBlk<false>{}));
+  MULTI_DISPATCH(W, MULTI_FLAG(op.vcol(), VCOL, hipLaunchKernelGGL((k_m_precond<MW, VCOL>), dim3(g), dim3(SCSAMD_BLOCK), 0, stream, v, op.rx,
+                                                                   op.ry, pd, Minv, val_blk<VCOL>(op.vAt, (eoff)At.bias))));
 }
 
-// G X on blocks (private.c:106-119 per column); dot_partials as in launch_spmm's EPI_GP.  rxb / ryb (both or neither): R_x / R_y
-// per column as n x W / m x W blocks instead of the workspace's own.  vA / vAt / vP (all, vP with P only, or none): every column
-// its own values of A, A' and P (value blocks at width W) instead of the workspace's; needs rxb / ryb.
-void LinSys::mat_vec_multi_dev(int W, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip, const real *rxb,
-                               const real *ryb, const real *vA, const real *vAt, const real *vP) {
+// G X on blocks (private.c:106-119 per column) under op; dot_partials as in launch_spmm's EPI_GP
+void LinSys::mat_vec_multi_dev(int W, const MultiOp &op, const real *X, real *Y, real *dot_partials, const int *cskip, const int *allskip) {
   MultiWork &mw = *multi;
   real *tmpb = mw.gt.p + (size_t)n * mw.width;
-  const bool percol = rxb != nullptr;
-  EpiArgs e1{percol ? ryb : ry.p, nullptr, nullptr, nullptr};
-  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip, percol, vA);
+  const bool percol = op.percol();
+  EpiArgs e1{percol ? op.ry : ry.p, nullptr, nullptr, nullptr};
+  launch_spmm(W, EPI_DIV, A, X, tmpb, e1, cskip, allskip, percol, op.vA);
   if (has_P) {
     EpiArgs ep{nullptr, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_PLAIN, P, X, mw.Pp.p, ep, cskip, allskip, false, vP);
+    launch_spmm(W, EPI_PLAIN, P, X, mw.Pp.p, ep, cskip, allskip, false, op.vP);
   }
-  EpiArgs e2{percol ? rxb : rx.p, X, has_P ? mw.Pp.p : nullptr, dot_partials};
-  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip, percol, vAt);
+  EpiArgs e2{percol ? op.rx : rx.p, X, has_P ? mw.Pp.p : nullptr, dot_partials};
+  launch_spmm(W, EPI_GP, At, tmpb, Y, e2, cskip, allskip, percol, op.vAt);
   n_matvecs++;
 }
 
-// K columns (2 <= K <= W) held in multi->bx / by (and multi->s when warm) in the block layout: [r_x; r_y] -> [x; y] in place
-void LinSys::solve_multi_dev(int K, int W, bool warm, const real *tolv, int *iters_out) {
-  MultiWork &mw = *multi;
-  MultiRhs a;
-  a.bx = mw.bx.p;
-  a.by = mw.by.p;
-  a.s = warm ? mw.s.p : nullptr;
-  solve_multi_blocks(K, W, a, tolv, iters_out);
+// The launchers of the vector kernels that have per-column forms: op.percol() and, for k_m_rhs_prep, "one warm-scale per column"
+// become the template arguments; R_y and the preconditioner are op's blocks or the workspace's vectors accordingly.
+template <typename WS>
+static void launch_rhs_prep_ws(LinSys &ls, int W, int K, const MultiRhs &a, real *tmp, const TolArgs &ta, int max_its, int g, WS ws) {
+  MultiWork &mw = *ls.multi;
+  const real *ry = a.op.percol() ? a.op.ry : ls.ry.p;
+  MULTI_DISPATCH(W, MULTI_FLAG(a.op.percol(), PERCOL,
+                               hipLaunchKernelGGL((k_m_rhs_prep<MW, PERCOL, WS>), dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, a.bx, a.by, ry,
+                                                  tmp, ls.n, ls.m, mw.part_max.p, g, mw.ctl.p, ta, K, max_its,
+                                                  a.warm_part, a.warm_cnt, ws, a.pre_stopped)));
+}
+static void launch_rhs_prep(LinSys &ls, int W, int K, const MultiRhs &a, real *tmp, const TolArgs &ta, int max_its, int g) {
+  if (!a.warm_scale_col) return launch_rhs_prep_ws(ls, W, K, a, tmp, ta, max_its, g, a.warm_scale);
+  TolArgs ws{}; // every column its own factor of the warm-start term
+  for (int k = 0; k < W; ++k) ws.t[k] = a.warm_scale_col[k];
+  launch_rhs_prep_ws(ls, W, K, a, tmp, ta, max_its, g, ws);
+}
+static void launch_cg_init(LinSys &ls, int W, const MultiRhs &a, int g) {
+  MultiWork &mw = *ls.multi;
+  const real *Minv = a.op.percol() ? a.op.Minv : ls.M.p;
+  MULTI_DISPATCH(W, MULTI_FLAG(a.op.percol(), PERCOL,
+                               hipLaunchKernelGGL((k_m_cg_init<MW, PERCOL>), dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, a.bx, a.s, mw.r.p, mw.z.p,
+                                                  Minv, ls.n, mw.part_ztr.p, mw.part_max.p, mw.ctl.p)));
+}
+static void launch_cg_update(LinSys &ls, int W, const MultiRhs &a, const real *Gp, int g, int cnt_pgp, int parity) {
+  MultiWork &mw = *ls.multi;
+  const real *Minv = a.op.percol() ? a.op.Minv : ls.M.p;
+  MULTI_DISPATCH(W, MULTI_FLAG(a.op.percol(), PERCOL,
+                               hipLaunchKernelGGL((k_m_cg_update<MW, PERCOL>), dim3(g), dim3(SCSAMD_BLOCK), 0, ls.stream, a.bx, mw.r.p, mw.z.p,
+                                                  mw.p.p, Gp, Minv, ls.n, mw.part_pgp.p, cnt_pgp, mw.part_ztr.p, mw.part_max.p, mw.ctl.p,
+                                                  parity)));
 }
 
-// the same on blocks the caller holds (a.bx: n x W, a.by: m x W, a.s: n x W or null), with the options of MultiRhs (linsys.h)
+// K columns (2 <= K <= W) on blocks the caller holds (a.bx: n x W, a.by: m x W, a.s: n x W or null): [r_x; r_y] -> [x; y] in place,
+// with the options of MultiRhs and under the operator a.op (linsys.h).  The steps are those of private.c:284-324 per column:
+// |b|_inf, the zero test and tmp = R_y^-1 r_y, b_x += A' tmp, r = G s when warm, the first residual, p = z, the iteration in
+// batches, y.
 void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tolv, int *iters_out) {
   MultiWork &mw = *multi;
   const bool warm = a.s != nullptr;
-  const bool percol = a.rx != nullptr; // every column under its own R_x / R_y / preconditioner: the workspace's rx, ry, M are not read
-  if (percol != (a.ry != nullptr) || percol != (a.Minv != nullptr)) throw HipError("scs_amd: per-column R needs rx, ry and Minv together");
-  // every column its own values of A, A' and P: the workspace's A.val, At.val, P.val (and, with percol, rx, ry, M) are read nowhere below
-  const bool vcol = a.vA != nullptr;
-  if (vcol != (a.vAt != nullptr) || (vcol && has_P) != (a.vP != nullptr)) throw HipError("scs_amd: per-column values need vA, vAt and, with P, vP");
-  if (vcol && !percol) throw HipError("scs_amd: per-column values run under per-column R");
+  const MultiOp &op = a.op;
+  op.check(has_P);
+  const bool percol = op.percol();
   real *const bx = a.bx, *const by = a.by;
   const int gv = vec_grid((long long)n * W), gnm = vec_grid(((long long)n + m) * W);
   CgCtlM *c = mw.ctl.p;
@@ -550,34 +572,13 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
   for (int k = 0; k < K; ++k) ta.t[k] = tolv[k];
   const size_t nx = (size_t)n * W, ny = (size_t)m * W;
   const long long mv0 = n_matvecs;
+  const EpiArgs none{nullptr, nullptr, nullptr, nullptr}, by_ry{percol ? op.ry : ry.p, nullptr, nullptr, nullptr};
 
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_absmax<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, nx, by, ny, mw.part_max.p));
-  if (a.warm_scale_col) { // every column its own factor of the warm-start term
-    TolArgs ws{};
-    for (int k = 0; k < W; ++k) ws.t[k] = a.warm_scale_col[k];
-    if (percol)
-      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, true, TolArgs>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, a.ry, tmpb, n,
-                                           m, mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, ws, a.pre_stopped));
-    else
-      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, false, TolArgs>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, ry.p, tmpb, n,
-                                           m, mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, ws, a.pre_stopped));
-  } else if (percol)
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_rhs_prep<MW, true>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, a.ry, tmpb, n, m,
-                                         mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
-  else
-    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rhs_prep<MW>, dim3(gnm), dim3(SCSAMD_BLOCK), 0, stream, bx, by, ry.p, tmpb, n, m,
-                                         mw.part_max.p, gnm, c, ta, K, max_its, a.warm_part, a.warm_cnt, a.warm_scale, a.pre_stopped));
-  { // b_x += A' R_y^-1 r_y   (private.c:305)
-    EpiArgs e{nullptr, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_ACC, At, tmpb, bx, e, zero, all, false, a.vAt);
-  }
-  if (warm) mat_vec_multi_dev(W, a.s, mw.r.p, nullptr, zero, all, a.rx, a.ry, a.vA, a.vAt, a.vP); // r = G s  (private.c:153)
-  if (percol)
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_cg_init<MW, true>), dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
-                                         mw.z.p, a.Minv, n, mw.part_ztr.p, mw.part_max.p, c));
-  else
-    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_init<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, a.s, mw.r.p,
-                                         mw.z.p, M.p, n, mw.part_ztr.p, mw.part_max.p, c));
+  launch_rhs_prep(*this, W, K, a, tmpb, ta, max_its, gnm);
+  launch_spmm(W, EPI_ACC, At, tmpb, bx, none, zero, all, false, op.vAt);           // b_x += A' R_y^-1 r_y   (private.c:305)
+  if (warm) mat_vec_multi_dev(W, op, a.s, mw.r.p, nullptr, zero, all);             // r = G s  (private.c:153)
+  launch_cg_init(*this, W, a, gv);
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_start<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                        mw.part_max.p, gv, c));
   // iteration batches: one control record read per batch, as solve_dev does with cg_pace=0 (every column's own count has to be
@@ -590,13 +591,8 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
     if (nb < 1) nb = 1;
     for (int j = 0; j < nb; ++j) {
       const int q = (int)((it + j) & 1);
-      mat_vec_multi_dev(W, mw.p.p, Gp, mw.part_pgp.p, done, all, a.rx, a.ry, a.vA, a.vAt, a.vP);
-      if (percol)
-        MULTI_DISPATCH(W, hipLaunchKernelGGL((k_m_cg_update<MW, true>), dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p,
-                                             Gp, a.Minv, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
-      else
-        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_update<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, bx, mw.r.p, mw.z.p, mw.p.p, Gp,
-                                             M.p, n, mw.part_pgp.p, gp, mw.part_ztr.p, mw.part_max.p, c, q));
+      mat_vec_multi_dev(W, op, mw.p.p, Gp, mw.part_pgp.p, done, all);
+      launch_cg_update(*this, W, a, Gp, gv, gp, q);
       MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cg_direction<MW>, dim3(gv), dim3(SCSAMD_BLOCK), 0, stream, mw.p.p, mw.z.p, n, mw.part_ztr.p,
                                            mw.part_max.p, gv, c, q));
     }
@@ -606,10 +602,7 @@ void LinSys::solve_multi_blocks(int K, int W, const MultiRhs &a, const real *tol
     if (mw.hctl.p->all_done || it >= max_its) break;
     batch = std::max(4, std::min(mw.last_its / 4 + 1, 1024));
   }
-  { // y = R_y^-1 (A x - r_y)   (private.c:313-317)
-    EpiArgs e{percol ? a.ry : ry.p, nullptr, nullptr, nullptr};
-    launch_spmm(W, EPI_NEGDIV, A, bx, by, e, zero, nullptr, percol, a.vA);
-  }
+  launch_spmm(W, EPI_NEGDIV, A, bx, by, by_ry, zero, nullptr, percol, op.vA); // y = R_y^-1 (A x - r_y)   (private.c:313-317)
   HIP_CHECK(hipGetLastError());
   int most = 0;
   for (int k = 0; k < K; ++k) {

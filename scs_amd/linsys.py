@@ -158,26 +158,16 @@ class LinSys:
             Dv = np.asfortranarray(diag_r, dtype=T.np_float)
             if not np.all(Dv > 0):  # an entry that underflows in the library's precision
                 raise ValueError("diag_r must be positive in the library's precision")
+        fp = lambda v: None if v is None else v.ctypes.data_as(T.fp)
+        lead = (fp(Dv), self.n + self.m)  # the DR pair that the two per-column entries take in front of B
         if own_values:
-            rc = self._lib.scs_amd_solve_lin_sys_multi_v(w, K, Dv.ctypes.data_as(T.fp) if Dv is not None else None, self.n + self.m,
-                                                         out.ctypes.data_as(T.fp), self.n + self.m,
-                                                         Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
-                                                         tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
-            if rc != 0:
-                raise ValueError("scs_amd_solve_lin_sys_multi_v refused the call")
-            return out, iters.astype(np.int64)
-        if diag_r is not None:
-            rc = self._lib.scs_amd_solve_lin_sys_multi_r(w, K, Dv.ctypes.data_as(T.fp), self.n + self.m, out.ctypes.data_as(T.fp),
-                                                         self.n + self.m, Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
-                                                         tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
-            if rc != 0:
-                raise RuntimeError("scs_amd_solve_lin_sys_multi_r failed")
-            return out, iters.astype(np.int64)
-        rc = self._lib.scs_amd_solve_lin_sys_multi(w, K, out.ctypes.data_as(T.fp), self.n + self.m,
-                                                   Sv.ctypes.data_as(T.fp) if Sv is not None else None, self.n,
-                                                   tv.ctypes.data_as(T.fp), iters.ctypes.data_as(T.ip))
-        if rc != 0:
-            raise RuntimeError("scs_amd_solve_lin_sys_multi failed")
+            entry, failure = self._lib.scs_amd_solve_lin_sys_multi_v, ValueError("scs_amd_solve_lin_sys_multi_v refused the call")
+        elif diag_r is not None:
+            entry, failure = self._lib.scs_amd_solve_lin_sys_multi_r, RuntimeError("scs_amd_solve_lin_sys_multi_r failed")
+        else:
+            entry, lead, failure = self._lib.scs_amd_solve_lin_sys_multi, (), RuntimeError("scs_amd_solve_lin_sys_multi failed")
+        if entry(w, K, *lead, fp(out), self.n + self.m, fp(Sv), self.n, fp(tv), iters.ctypes.data_as(T.ip)) != 0:
+            raise failure
         return out, iters.astype(np.int64)
 
     def update_diag_r(self, d):
