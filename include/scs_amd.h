@@ -564,6 +564,48 @@ scs_int scs_amd_solve_family_stream(ScsWork *w, scs_int nprob,
                                     ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
 const char *scs_amd_solve_family_stream_refusal(const ScsWork *w, scs_int own_scale);
 void scs_amd_family_stream_get_counters(const ScsWork *w, long long out[6]);
+/* ---- a family that shares the pattern and the cones but not the VALUES of A and P ----
+ * scs_amd_solve_family_scaled with one more difference: column k has its own A_k and P_k on the pattern given to scs_init (time-
+ * varying dynamics, scenario coefficients, a sweep over a coefficient).  Two calls, set once and solve any number of times:
+ * scs_amd_family_set_values: AX is nnz(A) x nprob, PX nnz(upper P) x nprob (given exactly when the workspace has a P), column-major
+ * host arrays with leading dimensions ldax / ldpx, every column in the CSC order of the d->A / d->P given to scs_init, as for
+ * scs_amd_update_matrix.  1 <= nprob <= 16 (no chunks: set and solve in groups, as scs_amd_linsys_set_values_multi).  Per column it
+ * runs scs_init's value-dependent half on scratch copies: the internal numbering, the equilibration passes scs_init took (so its own
+ * D_k, E_k), the box cone's normalised bounds, and the equilibrated values into the linear system's value blocks.  One column at a
+ * time; returns with the stream idle.  The workspace's own problem -- its values, D, E, scales, diag_r, preconditioner, captured
+ * graph, cone state -- is neither read for the columns nor written.
+ * scs_amd_solve_family_values: B, Cc, scales, sols, infos, warm_start as in scs_amd_solve_family_scaled (scales NULL: stgs.scale
+ * in every column; adaptive_scale is served per column), nprob that of the set call.  The contract:
+ *  - column k is scs_amd_update_matrix(w, AX[:,k], PX[:,k]); scs_update(w, B[:,k], Cc[:,k]); scs_solve(...) on a workspace at the
+ *    column's starting scale;
+ *  - bit for bit, column k is column k of scs_amd_solve_family_scaled, at the same nprob, on a workspace brought to values k by
+ *    scs_amd_update_matrix: (x, y, s), status_val, iter, scale, scale_updates and the residual and objective fields;
+ *  - with the workspace's own values in every column the call returns the bits of scs_amd_solve_family_scaled;
+ *  - a column depends neither on its neighbours' values nor on its position;
+ *  - scs_solve and the other family entries return the same bits before and after either call.
+ * Refused with SCS_FAILED before any device call, sols / infos untouched, the message from scs_amd_solve_family_values_refusal
+ * (which serves both calls; NULL when the last call was accepted): acceleration_lookback != 0 or log_csv_filename; a NULL among w,
+ * AX, B, Cc, sols, infos; PX given without a P or missing with one; nprob outside 1 .. 16; a short leading dimension; a matrix
+ * value that is not finite; a scale that is not finite and > 0; a solve before a set call or with another nprob than the set
+ * call's; a workspace that is stale after a failed scs_amd_update_matrix.  A scs_amd_update_matrix on the workspace leaves the
+ * stored blocks in force, as scs_amd_linsys_update_values does for the linear system's blocks.
+ * Memory: the value blocks of scs_amd_linsys_set_values_multi (2 nnz(A) W + nnz(full P) W + n W) plus (m + n) W for D / E,
+ * 2 (bsize - 1) W for the box bounds and nprob host copies of D, E; allocated by the first set call only, released by
+ * scs_amd_family_free_values (NULL-safe) or scs_finish; a failed allocation leaves the workspace usable with no values set.
+ * Host memory while the set call runs, released when it returns: scratch copies of A and P (their patterns and one column of
+ * values), the equilibrated values of all columns (nprob (nnz(A) + nnz(upper P)) values, handed to the value blocks in one go) and
+ * the (m + n) W host images of the D / E blocks.  The value blocks are those scs_amd_linsys_set_values_multi fills on a
+ * ScsLinSysWork; a ScsWork hands out no ScsLinSysWork, so on it only the set call above writes them.
+ * Not served: the stream entry, more than 16 columns in a call, Anderson acceleration, a row-sharded system.
+ * scs_amd_box_bounds is a TEST / DIAGNOSTIC entry, not part of the solver interface: host only, it returns the normalised bounds
+ * scs_init and the set call keep for a box cone whose bsize rows are scaled by Db (NULL: as given), so that arithmetic can be
+ * checked without a device. */
+scs_int scs_amd_family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx);
+scs_int scs_amd_solve_family_values(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
+void scs_amd_family_free_values(ScsWork *w);
+const char *scs_amd_solve_family_values_refusal(const ScsWork *w);
+scs_int scs_amd_box_bounds(const ScsCone *k, const scs_float *Db, scs_float *bl, scs_float *bu);
 /* What scs_init decided about its internal numbering (scs_amd/csrc/reorder.h: variables, the rows of the zero / nonnegative
  * cones and -- round 6 -- the rows behind the first one of a second-order cone may be renumbered so that the gathers of the CSR products of linsys/scs_matrix.c:161-186 share cache lines; callers never see
  * it -- b, c, warm starts and the returned (x, y, s) are mapped at this boundary).  out[0] = 1 if renumbered, out[1], out[2] =

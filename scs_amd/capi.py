@@ -238,6 +238,17 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_solve_family_stream_refusal.argtypes = [C.c_void_p, scs_int]
             lib.scs_amd_family_stream_get_counters.restype = None
             lib.scs_amd_family_stream_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 6)]
+            # ... whose columns have their own values of A and P
+            lib.scs_amd_family_set_values.restype = scs_int
+            lib.scs_amd_family_set_values.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int]
+            lib.scs_amd_solve_family_values.restype = scs_int
+            lib.scs_amd_solve_family_values.argtypes = lib.scs_amd_solve_family_scaled.argtypes
+            lib.scs_amd_family_free_values.restype = None
+            lib.scs_amd_family_free_values.argtypes = [C.c_void_p]
+            lib.scs_amd_solve_family_values_refusal.restype = C.c_char_p
+            lib.scs_amd_solve_family_values_refusal.argtypes = [C.c_void_p]
+            lib.scs_amd_box_bounds.restype = scs_int
+            lib.scs_amd_box_bounds.argtypes = [C.POINTER(T.ScsCone), fp, fp, fp]
             # a block of Anderson accelerations at once (include/scs_amd.h; scs_amd/accel.py is the object form)
             lib.scs_amd_aa_multi_width.restype = scs_int
             lib.scs_amd_aa_multi_width.argtypes = [scs_int]
@@ -541,7 +552,47 @@ def family_stream_counters(lib, w):
     return dict(zip(("block_iters", "run_slot_iters", "idle_slot_iters", "refills", "resid_evals", "width"), (int(v) for v in out)))
 
 
-def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales, stream_width=None):
+def values_block(V, nnz, what, f):
+    """V as the nnz x K column-major block of the family's value entries: a 2-D array of K columns of `nnz` (None: any number of) finite
+    values, 1 <= K <= 16.
+    ValueError otherwise; the library is not called."""
+    V = np.asarray(V, dtype=f)
+    if V.ndim != 2 or (nnz is not None and V.shape[0] != nnz):
+        raise ValueError(f"{what} must be a 2-D array with one row per stored entry ({nnz}) and one column per problem")
+    if not 1 <= V.shape[1] <= 16:
+        raise ValueError(f"{what} must have 1 .. 16 columns (set and solve in groups)")
+    if not np.all(np.isfinite(V)):
+        raise ValueError(f"{what}: matrix values must be finite")
+    return np.asfortranarray(V)
+
+
+def family_set_values(lib, w, AX, PX=None):
+    """scs_amd_family_set_values: AX (nnz(A) x K) and, for a workspace with P, PX (nnz(upper P) x K), the values of every column's
+    matrices in the CSC order of the matrices given to scs_init.  Shapes and finiteness are checked here (ValueError); whether PX
+    goes with the workspace is the library's check.  Returns rc."""
+    T = lib._scs_types
+    AX = values_block(AX, None, "AX", T.np_float)
+    px, ldp = None, 0
+    if PX is not None:
+        PX = values_block(PX, None, "PX", T.np_float)
+        if PX.shape[1] != AX.shape[1]:
+            raise ValueError("AX and PX must have the same number of columns")
+        px, ldp = PX.ctypes.data_as(T.fp), max(PX.shape[0], 1)
+    return lib.scs_amd_family_set_values(w, AX.shape[1], AX.ctypes.data_as(T.fp), max(AX.shape[0], 1), px, ldp)
+
+
+def family_free_values(lib, w):
+    """scs_amd_family_free_values: releases what family_set_values allocated; a solve_family_values is refused until the next set"""
+    lib.scs_amd_family_free_values(w)
+
+
+def solve_family_values(lib, w, B, Cc, scales=None, warm=None, warm_start=None):
+    """scs_amd_solve_family_values: solve_family_scaled with column k under the values of the last family_set_values; K must be that
+    call's.  Arguments and return as solve_family_scaled."""
+    return _solve_family(lib, w, B, Cc, warm, warm_start, True, scales, values=True)
+
+
+def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales, stream_width=None, values=False):
     T = lib._scs_types
     f = T.np_float
     B = np.asfortranarray(np.asarray(B, dtype=f))
@@ -570,6 +621,8 @@ def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales, stream_width=
     if stream_width is not None:
         rc = lib.scs_amd_solve_family_stream(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, 1 if scaled else 0, sp,
                                              stream_width, sols, infos, ws)
+    elif values:
+        rc = lib.scs_amd_solve_family_values(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sp, sols, infos, ws)
     elif scaled:
         rc = lib.scs_amd_solve_family_scaled(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sp, sols, infos, ws)
     else:

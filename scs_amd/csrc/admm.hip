@@ -397,6 +397,7 @@ struct SCS_WORK {
   long long cone_projs = 0;
   FamilyWork *fam = nullptr;
   const char *stream_arg_refusal = nullptr; // why the last scs_amd_solve_family_stream refused its arguments (a literal), or null
+  const char *values_arg_refusal = nullptr; // the same for scs_amd_family_set_values / scs_amd_solve_family_values
   // scs_amd_update_matrix: what an update needs beyond the above
   real scale0 = 0;               // stgs.scale as given to scs_init (an adaptive-scale solve moves stgs.scale; an update puts it back)
   bool dev_eq = false;           // where scs_init equilibrated: an update takes the same passes

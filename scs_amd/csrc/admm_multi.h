@@ -63,6 +63,13 @@
 // PSD blocks are refused: the LDS eigensolver's warm flag is one per launch and its cold-restart counter belongs to the width.
 // Every problem that passes through a stream has, bit for bit, what the entry of the same form returns for it in a call of the
 // same width: the guarantee above (no dependence on neighbours or position) is what makes that an exact yardstick.
+//
+// A fourth entry, the scaled loop for problems that share the pattern and the cones but not the VALUES of A and P.
+// scs_amd_family_set_values runs scs_init's value-dependent half once per column (scs_amd_update_matrix's code on scratch copies: the
+// internal numbering, the equilibration, D_k / E_k, the box cone's bounds) and stores the equilibrated values in the linear system's
+// value blocks; scs_amd_solve_family_values is family_chunk<true, true>, where the products, the preconditioner, D / E in the
+// residuals, the Scaling of the host steps and the box bounds are the column's own (VC, DCOL).  Column k is, bit for bit, column k of
+// the scaled entry on a workspace brought to values k by scs_amd_update_matrix.  At most 16 problems, no stream form.
 #pragma once
 
 namespace scsamd {
@@ -334,7 +341,9 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_remap_v(real *v, const real 
 }
 
 // ---- residuals per column: the quantities Q_* of admm.hip -> part[(q * stride + workgroup) * W + column] --------------------
-template <int W>
+// DCOL (here and in k_f_resid_dual; scs_amd_solve_family_values): D / E are m x W / n x W blocks, every column its own equilibration,
+// instead of one vector -- D[f] where the shared form reads D[f / W], in the same expressions.
+template <int W, bool DCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_primal(const real *__restrict__ ax, const real *__restrict__ s,
                                                                  const real *__restrict__ y, const real *__restrict__ b,
                                                                  const real *__restrict__ D, const real *tau_row, int m, real *part,
@@ -346,7 +355,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_primal(const real *__r
     const real tau = absval(tau_row[col]), ds = ctl->ds[col], inv_ds = (real)1.0 / ds;
     const size_t tot = (size_t)m * W, gs = (size_t)gridDim.x * blockDim.x;
     for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
-      const real axi = ax[f], si = s[f], bi = b[f], Di = D[f / W];
+      const real axi = ax[f], si = s[f], bi = b[f], Di = D[DCOL ? f : f / W];
       const real axs = axi + si;
       const real pri = axs - tau * bi;
       const real fo = inv_ds / Di;
@@ -374,7 +383,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_primal(const real *__r
   }
 }
 
-template <int W>
+template <int W, bool DCOL = false>
 __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_dual(const real *px, const real *__restrict__ aty, const real *__restrict__ x,
                                                                const real *__restrict__ c, const real *__restrict__ E, const real *tau_row,
                                                                int n, real *part, int stride, const FamCtl *ctl) {
@@ -387,7 +396,7 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_dual(const real *px, c
     for (size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x; f < tot; f += gs) {
       const real pxi = px ? px[f] : (real)0, ai = aty[f], xi = x[f], ci = c[f];
       const real dual = pxi + ai + tau * ci;
-      const real fo = inv_ps / E[f / W];
+      const real fo = inv_ps / E[DCOL ? f : f / W];
       real a;
       a = absval(dual); q_d = a > q_d ? a : q_d;
       a = absval(pxi); q_px = a > q_px ? a : q_px;
@@ -458,6 +467,19 @@ struct FamilyWork {
   DevBuf<real> stage, outb;
   std::vector<real> hstage, hout;
   long long counters[6] = {0, 0, 0, 0, 0, 0};
+  // scs_amd_solve_family_values only, allocated by scs_amd_family_set_values: what scs_init derives from the values, per column.
+  // The equilibrated values themselves are the linear system's value blocks (MultiWork::vA ...), which nothing else can reach on a
+  // ScsWork: scs_amd_linsys_set_values_multi takes a ScsLinSysWork.
+  int vwidth = 0;            // width the four blocks below were allocated for (0: not allocated)
+  int vcols = 0, vlayout = 0; // columns and layout width of the set call in force (0: none)
+  DevBuf<real> vD, vE;       // m x W, n x W: D_k, E_k; padding columns 1
+  DevBuf<real> vbl, vbu;     // the box cone's normalised bounds, column k's bsize - 1 values at k * (bsize - 1); only with a box cone
+  std::vector<Scaling> vscal; // every column's D, E on the host (its primal / dual scale belongs to a solve: FamCol::ps / ds)
+  void free_values() {
+    vwidth = vcols = vlayout = 0;
+    for (DevBuf<real> *b : {&vD, &vE, &vbl, &vbu}) b->release();
+    vscal = std::vector<Scaling>();
+  }
 };
 static void family_free(FamilyWork *f) { delete f; }
 
@@ -535,7 +557,8 @@ static const char *family_refusal(const ScsWork *w, bool scaled = false) {
 
 // one residual evaluation for all running columns, one read-back (populate_residuals on blocks)
 // iter: the global iteration; column k is told its own, iter - cols[k].start.  only: the columns whose records are filled
-static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter, unsigned only = ~0u) {
+// vc: every column under its own values and its own D / E (the blocks of scs_amd_family_set_values)
+static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter, unsigned only = ~0u, bool vc = false) {
   FamilyWork &f = *w->fam;
   const int n = w->n, m = w->m, l = w->l;
   hipStream_t st = w->stream;
@@ -544,14 +567,16 @@ static void family_residuals(ScsWork *w, int W, int K, FamCol *cols, int iter, u
   const real *tau_row = f.u.p + (size_t)(l - 1) * W, *kap_row = f.rsk.p + (size_t)(l - 1) * W;
   const int *frozen = f.ctl.p->frozen;
   const EpiArgs e{nullptr, nullptr, nullptr, nullptr};
-  w->ls.launch_spmm(W, EPI_PLAIN, w->ls.A, x, f.ax.p, e, frozen, nullptr);
-  w->ls.launch_spmm(W, EPI_PLAIN, w->ls.At, y, f.aty.p, e, frozen, nullptr);
-  if (w->has_P) w->ls.launch_spmm(W, EPI_PLAIN, w->ls.P, x, f.px.p, e, frozen, nullptr);
+  const MultiOp vals = vc ? MultiOp::of_work(*w->ls.multi, true, w->has_P) : MultiOp::shared(); // the value blocks only: no R in a residual
+  w->ls.launch_spmm(W, EPI_PLAIN, w->ls.A, x, f.ax.p, e, frozen, nullptr, false, vals.vA);
+  w->ls.launch_spmm(W, EPI_PLAIN, w->ls.At, y, f.aty.p, e, frozen, nullptr, false, vals.vAt);
+  if (w->has_P) w->ls.launch_spmm(W, EPI_PLAIN, w->ls.P, x, f.px.p, e, frozen, nullptr, false, vals.vP);
   const int gm = glue_grid((long long)m * W), gn = glue_grid((long long)n * W);
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_primal<MW>, dim3(gm), dim3(SCSAMD_BLOCK), 0, st, f.ax.p, s, y, f.b.p, w->D.p, tau_row, m,
-                                       f.part.p, PSTRIDE, f.ctl.p));
-  MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_dual<MW>, dim3(gn), dim3(SCSAMD_BLOCK), 0, st, w->has_P ? f.px.p : (const real *)nullptr,
-                                       f.aty.p, x, f.c.p, w->E.p, tau_row, n, f.part.p, PSTRIDE, f.ctl.p));
+  MULTI_DISPATCH(W, MULTI_FLAG(vc, DCOL, hipLaunchKernelGGL((k_f_resid_primal<MW, DCOL>), dim3(gm), dim3(SCSAMD_BLOCK), 0, st, f.ax.p, s, y, f.b.p,
+                                                            vc ? f.vD.p : w->D.p, tau_row, m, f.part.p, PSTRIDE, f.ctl.p)));
+  MULTI_DISPATCH(W, MULTI_FLAG(vc, DCOL, hipLaunchKernelGGL((k_f_resid_dual<MW, DCOL>), dim3(gn), dim3(SCSAMD_BLOCK), 0, st,
+                                                            w->has_P ? f.px.p : (const real *)nullptr, f.aty.p, x, f.c.p,
+                                                            vc ? f.vE.p : w->E.p, tau_row, n, f.part.p, PSTRIDE, f.ctl.p)));
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_resid_final<MW>, dim3(1), dim3(SCSAMD_BLOCK), 0, st, f.part.p, PSTRIDE, gm, gn, tau_row, kap_row,
                                        f.qout.p, f.ctl.p));
   HIP_CHECK(hipMemcpyAsync(f.hq.p, f.qout.p, (size_t)NQ * W * sizeof(real), hipMemcpyDeviceToHost, st));
@@ -581,8 +606,9 @@ static void family_upload_ctl(ScsWork *w, int W, int K, const FamCol *cols, int 
 
 // ---- the host arithmetic of one problem, shared by the chunk loop and the stream loop (staging: f.col_x / col_y / col_s) -----
 // scs_update (:1287-1325): renumber, the norms of the data as given, normalize_b_c with the problem's own sigma.  Leaves b in
-// f.col_y and c in f.col_x, in the internal numbering, and the problem's scales and norms in col.
-static void family_stage_data(ScsWork *w, const real *bk, const real *ck, FamCol &col) {
+// f.col_y and c in f.col_x, in the internal numbering, and the problem's scales and norms in col.  sc: the D, E the problem's
+// matrices were equilibrated with -- the workspace's, or the column's own (scs_amd_solve_family_values); here and in the two below.
+static void family_stage_data(ScsWork *w, const Scaling &sc, const real *bk, const real *ck, FamCol &col) {
   FamilyWork &f = *w->fam;
   const int n = w->n, m = w->m;
   const Reorder &ro = w->reord;
@@ -597,13 +623,13 @@ static void family_stage_data(ScsWork *w, const real *bk, const real *ck, FamCol
   for (int j = 0; j < n; ++j) nc = std::max(nc, (real)std::fabs(c[j]));
   col.nm_b_orig = nb;
   col.nm_c_orig = nc;
-  if (w->stgs.normalize) col.ps = col.ds = normalize_b_c_sigma(w->scal, b, c);
+  if (w->stgs.normalize) col.ps = col.ds = normalize_b_c_sigma(sc, b, c);
 }
 
 // solve_begin's warm start (:660-687): v = [x; y + s / R_y] from the caller's (x, y, s), normalised with the problem's scales.
 // ry, ry_stride: the problem's own R_y, row i at ry[i * ry_stride].  Leaves the x part in f.col_x and the y part in f.col_y; false
 // (nothing written) when the caller gave no start for this problem.
-static bool family_stage_warm(ScsWork *w, const ScsSolution &sol, const FamCol &col, const real *ry, size_t ry_stride) {
+static bool family_stage_warm(ScsWork *w, const Scaling &sc, const ScsSolution &sol, const FamCol &col, const real *ry, size_t ry_stride) {
   if (!sol.x || !sol.y || !sol.s) return false;
   FamilyWork &f = *w->fam;
   const int n = w->n, m = w->m;
@@ -615,10 +641,10 @@ static bool family_stage_warm(ScsWork *w, const ScsSolution &sol, const FamCol &
     s[i] = ro.active ? sol.s[ro.row_new2old[i]] : sol.s[i];
   }
   if (w->stgs.normalize) { // normalize_sol (src/normalize.c:64-76) with the problem's scales
-    for (int j = 0; j < n; ++j) x[j] /= (w->scal.E[j] / col.ds);
+    for (int j = 0; j < n; ++j) x[j] /= (sc.E[j] / col.ds);
     for (int i = 0; i < m; ++i) {
-      y[i] /= (w->scal.D[i] / col.ps);
-      s[i] *= (w->scal.D[i] * col.ds);
+      y[i] /= (sc.D[i] / col.ps);
+      s[i] *= (sc.D[i] * col.ds);
     }
   }
   for (int j = 0; j < n; ++j) x[j] = x[j] != x[j] ? (real)0 : x[j];
@@ -630,7 +656,7 @@ static bool family_stage_warm(ScsWork *w, const ScsSolution &sol, const FamCol &
 }
 
 // solve_end / finalize: the problem's normalised (x, y, s) in f.col_x / col_y / col_s, in the internal numbering -> sol and info
-static void family_return(ScsWork *w, const FamCol &col, bool own_scale, int time_limit_reached, double solve_ms, double lin_ms,
+static void family_return(ScsWork *w, const Scaling &sc, const FamCol &col, bool own_scale, int time_limit_reached, double solve_ms, double lin_ms,
                           double cone_ms, ScsSolution *sol, ScsInfo *info) {
   FamilyWork &f = *w->fam;
   const int n = w->n, m = w->m;
@@ -640,10 +666,10 @@ static void family_return(ScsWork *w, const FamCol &col, bool own_scale, int tim
   if (!sol->s) sol->s = (real *)calloc(m, sizeof(real));
   real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
   if (w->stgs.normalize) { // un_normalize_sol (src/normalize.c:78-91) with the problem's scales
-    for (int j = 0; j < n; ++j) x[j] *= (w->scal.E[j] / col.ds);
+    for (int j = 0; j < n; ++j) x[j] *= (sc.E[j] / col.ds);
     for (int r = 0; r < m; ++r) {
-      y[r] *= (w->scal.D[r] / col.ps);
-      s[r] /= (w->scal.D[r] * col.ds);
+      y[r] *= (sc.D[r] / col.ps);
+      s[r] /= (sc.D[r] * col.ds);
     }
   }
   for (int j = 0; j < n; ++j) sol->x[ro.active ? ro.col_new2old[j] : j] = x[j];
@@ -667,29 +693,33 @@ static void family_return(ScsWork *w, const FamCol &col, bool own_scale, int tim
   if (w->stgs.verbose) print_summary_row(col.r_o, col.iter, own_scale ? col.scale : w->stgs.scale, (solve_ms + w->setup_time) / 1e3);
 }
 
-// the operator of a family's block solves: with own scales the x and y rows of f.R and f.Minv, else the workspace's shared R
-static MultiOp family_op(const ScsWork *w, int W, bool own_r) {
-  return own_r ? MultiOp::r_rows(w->fam->R.p, (size_t)w->n * W, w->fam->Minv.p) : MultiOp::shared();
+// the operator of a family's block solves: with own scales the x and y rows of f.R and f.Minv, else the workspace's shared R;
+// vc: under them the linear system's value blocks, every column its own A and P
+static MultiOp family_op(const ScsWork *w, int W, bool own_r, bool vc = false) {
+  if (!own_r) return MultiOp::shared();
+  MultiOp o = vc ? MultiOp::of_work(*w->ls.multi, true, w->has_P) : MultiOp::shared();
+  o.rx = w->fam->R.p, o.ry = w->fam->R.p + (size_t)w->n * W, o.Minv = w->fam->Minv.p;
+  return o;
 }
 
 // the R of every column (padding: 1) from the scales of the control record, its preconditioner and the box cone's copy of its r_y
-static void family_apply_scales(ScsWork *w, int W, int K) {
+static void family_apply_scales(ScsWork *w, int W, int K, bool vc = false) {
   FamilyWork &f = *w->fam;
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_set_diag_r<MW>, dim3(glue_grid((long long)w->l * W)), dim3(SCSAMD_BLOCK), 0, w->stream, f.R.p, w->n,
                                          w->m, (int)w->k.z, w->stgs.rho_x, K, f.ctl.p));
-  w->ls.precond_multi_blocks(W, family_op(w, W, true), f.Minv.p);
+  w->ls.precond_multi_blocks(W, family_op(w, W, true, vc), f.Minv.p);
   w->cone.set_multi_ry(f.R.p + (size_t)w->n * W, W);
 }
 
 // update_work_cache per column: g = (R + M)^-1 [c; -b] to CG_BEST_TOL (:1118-1128).  `skip` (W ints on the device): the columns
 // whose g stays as it is -- not one bit of theirs is read or written
-static void family_update_g(ScsWork *w, int W, int K, bool own_r, const int *skip) {
+static void family_update_g(ScsWork *w, int W, int K, bool own_r, const int *skip, bool vc = false) {
   FamilyWork &f = *w->fam;
   MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_build_g<MW>, dim3(glue_grid((long long)(w->n + w->m) * W)), dim3(SCSAMD_BLOCK), 0, w->stream, f.g.p,
                                          f.c.p, f.b.p, w->n, w->m, skip));
   real tolv[MULTI_W_MAX];
   for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = (real)CG_BEST_TOL;
-  MultiRhs a(f.g.p, f.g.p + (size_t)w->n * W, nullptr, family_op(w, W, own_r));
+  MultiRhs a(f.g.p, f.g.p + (size_t)w->n * W, nullptr, family_op(w, W, own_r, vc));
   a.pre_stopped = skip;
   w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
 }
@@ -699,7 +729,10 @@ static void family_update_g(ScsWork *w, int W, int K, bool own_r, const int *ski
 // PC = false: scs_amd_solve_family, the columns share the workspace's diag_r.  PC = true: scs_amd_solve_family_scaled, column k
 // runs under its own diag_r_k from scales[k] (null: the workspace's stgs.scale in every column) and, with adaptive_scale, under its
 // own update_scale; the workspace's diag_r and the linear system's rx / ry / M are not read.
-template <bool PC>
+// VC (with PC only): scs_amd_solve_family_values, column k under its own A_k and P_k as well -- the blocks of the set call in force
+// (FamilyWork::vD ..., the linear system's value blocks) stand where the shared form reads the workspace's values, D, E, scal and box
+// bounds, which are then not read.
+template <bool PC, bool VC = false>
 static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, const real *Cc, size_t ldc, const real *scales,
                         ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
   const int n = w->n, m = w->m, l = w->l;
@@ -723,7 +756,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   f.hblk.assign(mw, (real)0);
   f.hblk2.assign(nw, (real)0);
   for (int k = 0; k < K; ++k) {
-    family_stage_data(w, B + (size_t)k * ldb, Cc + (size_t)k * ldc, cols[k]);
+    family_stage_data(w, VC ? f.vscal[k] : w->scal, B + (size_t)k * ldb, Cc + (size_t)k * ldc, cols[k]);
     for (int i = 0; i < m; ++i) f.hblk[(size_t)i * W + k] = f.col_y[i];
     for (int j = 0; j < n; ++j) f.hblk2[(size_t)j * W + k] = f.col_x[j];
   }
@@ -734,7 +767,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     cols[k].upd = PC;
   }
   family_upload_ctl(w, W, K, cols, PC ? 1 : 0);
-  if (PC) family_apply_scales(w, W, K);
+  if (PC) family_apply_scales(w, W, K, VC);
   for (int k = 0; k < K; ++k) cols[k].upd = false;
   HIP_CHECK(hipStreamSynchronize(st)); // the staging vectors are reused below
 
@@ -746,7 +779,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     else w->diag_r.download(hr.data(), l, st);
     HIP_CHECK(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) {
-      if (!family_stage_warm(w, sols[k], cols[k], PC ? hr.data() + (size_t)n * W + k : hr.data() + n, PC ? W : 1)) continue; // its own R_y
+      if (!family_stage_warm(w, VC ? f.vscal[k] : w->scal, sols[k], cols[k], PC ? hr.data() + (size_t)n * W + k : hr.data() + n, PC ? W : 1)) continue; // its own R_y
       for (int j = 0; j < n; ++j) f.hblk[(size_t)j * W + k] = f.col_x[j];
       for (int i = 0; i < m; ++i) f.hblk[(size_t)(n + i) * W + k] = f.col_y[i];
     }
@@ -763,7 +796,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   // ---- update_work_cache per column: g = (R + M)^-1 [c; -b] to CG_BEST_TOL (:1118-1128)
   const int *frozen = f.ctl.p->frozen;
   real tolv[MULTI_W_MAX];
-  family_update_g(w, W, K, PC, frozen);
+  family_update_g(w, W, K, PC, frozen, VC);
 
   // ---- the loop of src/scs.c:1356-1455 on blocks
   real *part = f.part.p, *nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, *warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
@@ -777,7 +810,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
                                          f.warm.p, n, l, nrm_part, gl, warm_part, do_norm, f.ctl.p));
     { // the linear system (:763), every column on its own tolerance schedule (:745-762)
       const double tl = now_ms();
-      MultiRhs a(f.u_t.p, f.u_t.p + nw, f.warm.p, family_op(w, W, PC));
+      MultiRhs a(f.u_t.p, f.u_t.p + nw, f.warm.p, family_op(w, W, PC, VC));
       a.pre_stopped = frozen;
       if (w->cg_tol_override > 0) {
         for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
@@ -798,7 +831,8 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
                                          f.cw.p, n, l, part, gnm, PSTRIDE, feas, f.ctl.p));
     int cslot = -1;
     if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
-    if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true); // the box cone under the column's own r_y
+    if (VC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true, f.vbl.p, f.vbu.p); // and between the column's own bounds
+    else if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true); // the box cone under the column's own r_y
     else w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
     w->cone_timer.stop(cslot, st);
     w->cone_projs++;
@@ -810,7 +844,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       sigint = true;
       break;
     }
-    family_residuals(w, W, K, cols, i);
+    family_residuals(w, W, K, cols, i, ~0u, VC);
     bool changed = false;
     for (int k = 0; k < K; ++k) {
       if (cols[k].frozen) continue;
@@ -845,8 +879,8 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       break;
     }
     if (rescaled) { // update_scale's device half for the columns in upd; of the others not one bit changes
-      family_apply_scales(w, W, K);
-      family_update_g(w, W, K, PC, f.ctl.p->keep);
+      family_apply_scales(w, W, K, VC);
+      family_update_g(w, W, K, PC, f.ctl.p->keep, VC);
       MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
       for (int k = 0; k < K; ++k) cols[k].upd = false;
     }
@@ -863,7 +897,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
         cols[k].iter = i;
         stale = stale || cols[k].r_n.last_iter != i;
       }
-    if (stale) family_residuals(w, W, K, cols, i);
+    if (stale) family_residuals(w, W, K, cols, i, ~0u, VC);
   }
   f.hblk.resize(lw);
   f.hblk2.resize(mw);
@@ -887,7 +921,7 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       y[r] = f.hblk[(size_t)(n + r) * W + k];
       s[r] = f.hblk2[(size_t)r * W + k];
     }
-    family_return(w, cols[k], PC, time_limit_reached, solve_ms, t_lin, cone_ms, sol, info);
+    family_return(w, VC ? f.vscal[k] : w->scal, cols[k], PC, time_limit_reached, solve_ms, t_lin, cone_ms, sol, info);
   }
   return sigint ? SCS_SIGINT : 0;
 }
@@ -1004,7 +1038,7 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       c.frozen = c.pending = !first; // the first columns run from iteration 0: nothing to wait for
       c.upd = true;                  // its R (PC) and its g are built below, with every other column left as it is
       c.scale = PC && scales ? scales[c.prob] : w->stgs.scale;
-      family_stage_data(w, B + (size_t)c.prob * ldb, Cc + (size_t)c.prob * ldc, c);
+      family_stage_data(w, w->scal, B + (size_t)c.prob * ldb, Cc + (size_t)c.prob * ldc, c);
       real *rec = f.hstage.data() + (size_t)k * rec_in;
       std::copy(f.col_y.begin(), f.col_y.end(), rec);
       std::copy(f.col_x.begin(), f.col_x.end(), rec + m);
@@ -1031,7 +1065,7 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       }
       for (int k = 0; k < K; ++k) {
         if (!((mask >> k) & 1u)) continue;
-        if (!family_stage_warm(w, sols[cols[k].prob], cols[k], PC ? hr.data() + nw + k : hr.data() + n, PC ? W : 1)) continue;
+        if (!family_stage_warm(w, w->scal, sols[cols[k].prob], cols[k], PC ? hr.data() + nw + k : hr.data() + n, PC ? W : 1)) continue;
         real *v = f.hstage.data() + (size_t)k * rec_in + m + n;
         std::copy(f.col_x.begin(), f.col_x.end(), v);
         std::copy(f.col_y.begin(), f.col_y.end(), v + n);
@@ -1064,7 +1098,7 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       std::copy(rec, rec + n, f.col_x.begin());
       std::copy(rec + n, rec + n + m, f.col_y.begin());
       std::copy(rec + n + m, rec + rec_out, f.col_s.begin());
-      family_return(w, c, PC, c.time_limit_reached, t1 - c.t0, t_lin - c.t_lin0, cone_iter_ms * std::max(c.iter, 1), &sols[c.prob],
+      family_return(w, w->scal, c, PC, c.time_limit_reached, t1 - c.t0, t_lin - c.t_lin0, cone_iter_ms * std::max(c.iter, 1), &sols[c.prob],
                     &infos[c.prob]);
       returned[c.prob] = 1;
       c.prob = -1;
@@ -1275,7 +1309,173 @@ static scs_int family_stream_solve(ScsWork *w, scs_int nprob, const scs_float *B
   return 0;
 }
 
+// ============================================================================
+// scs_amd_family_set_values / scs_amd_solve_family_values: a family that shares the pattern and the cones but not the values of A, P
+// ============================================================================
+// The set call is scs_init's value-dependent half per column, on scratch copies of the host matrices: values into the internal
+// numbering and equilibration exactly as scs_amd_update_matrix takes them, so column k's D_k, E_k and equilibrated values are, bit
+// for bit, those of a workspace brought to values k.  The solve call is family_chunk<true, true>: the loop of the scaled entry with
+// every input that follows the values -- the products, the preconditioner, D / E in the residuals, the Scaling of the host steps, the
+// box cone's bounds -- taken from the column's own.  Nothing of the workspace's own problem is read for a column or written.
+static scs_int family_values_refuse(ScsWork *w, const char *why) {
+  if (w) w->values_arg_refusal = why;
+  printf("ERROR: %s\n", why);
+  return SCS_FAILED;
+}
+
+static scs_int family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+  if (!w || !AX) return family_values_refuse(w, "scs_amd_family_set_values: w and AX must be given");
+  w->values_arg_refusal = nullptr;
+  if (const char *why = family_refusal(w, true)) {
+    printf("ERROR: %s\n", why);
+    return SCS_FAILED;
+  }
+  if ((PX != nullptr) != w->has_P) return family_values_refuse(w, "scs_amd_family_set_values: PX must be given exactly when the workspace has a P");
+  if (nprob < 1 || nprob > MULTI_W_MAX) return family_values_refuse(w, "scs_amd_family_set_values: nprob must be 1 .. 16 (set and solve in groups)");
+  const size_t nzA = w->A.x.size(), nzP = w->has_P ? w->P.x.size() : 0;
+  if ((long long)ldax < (long long)nzA || (PX && (long long)ldpx < (long long)nzP))
+    return family_values_refuse(w, "scs_amd_family_set_values: a leading dimension is shorter than its column");
+  for (scs_int k = 0; k < nprob; ++k)
+    if (!all_finite(AX + (size_t)k * (size_t)ldax, nzA) || (PX && !all_finite(PX + (size_t)k * (size_t)ldpx, nzP)))
+      return family_values_refuse(w, "scs_amd_family_set_values: a matrix value is not finite");
+  if (w->stale) return family_values_refuse(w, "scs_amd_family_set_values: the last scs_amd_update_matrix failed: update again first");
+  if (w->ls.shard) return family_values_refuse(w, "scs_amd_family_set_values: a row-sharded workspace takes no values per column");
+  const int K = (int)nprob, W = std::max(2, multi_width(K)), n = w->n, m = w->m;
+  const int nb = w->k.bsize > 1 ? (int)w->k.bsize - 1 : 0; // bounds of the box cone
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    if (!w->fam) w->fam = new FamilyWork();
+    FamilyWork &f = *w->fam;
+    f.vcols = 0; // a failure below leaves no set in force
+    if (f.vwidth < W) {
+      f.free_values();
+      f.vD.alloc((size_t)m * W);
+      f.vE.alloc((size_t)n * W);
+      if (nb) {
+        f.vbl.alloc((size_t)nb * W);
+        f.vbu.alloc((size_t)nb * W);
+      }
+      f.vwidth = W;
+    }
+    f.vscal.assign((size_t)K, Scaling());
+    const bool norm = w->stgs.normalize != 0;
+    HostCsc A2 = w->A, P2; // scratch: the workspace's own copies, D, E and scal stay as they are
+    if (w->has_P) P2 = w->P;
+    std::vector<real> ax(nzA * K), px(nzP * K), hD((size_t)m * W, (real)1), hE((size_t)n * W, (real)1), hbl((size_t)nb * W, (real)0),
+        hbu((size_t)nb * W, (real)0);
+    for (int k = 0; k < K; ++k) {
+      const real *a = AX + (size_t)k * (size_t)ldax, *p = PX ? PX + (size_t)k * (size_t)ldpx : nullptr;
+      if (norm && w->has_P) { // as scs_amd_update_matrix: P switches the renumbering off, the caller's order is the internal one
+        std::copy(a, a + nzA, A2.x.begin());
+        std::copy(p, p + nzP, P2.x.begin());
+      } else {
+        permute_values(w->reord, a, nzA, A2.x.data());
+        if (p) std::copy(p, p + nzP, P2.x.begin());
+      }
+      Scaling &sc = f.vscal[k];
+      if (norm) {
+        if (w->dev_eq) equilibrate_dev(w->has_P ? &P2 : nullptr, A2, &w->k, sc, w->stream, nullptr);
+        else equilibrate(w->has_P ? &P2 : nullptr, A2, &w->k, sc);
+      } else {
+        sc.D.assign(m, (real)1);
+        sc.E.assign(n, (real)1);
+      }
+      std::copy(A2.x.begin(), A2.x.end(), ax.begin() + (size_t)k * nzA);
+      if (w->has_P) std::copy(P2.x.begin(), P2.x.end(), px.begin() + (size_t)k * nzP);
+      for (int i = 0; i < m; ++i) hD[(size_t)i * W + k] = sc.D[i];
+      for (int j = 0; j < n; ++j) hE[(size_t)j * W + k] = sc.E[j];
+      if (nb) ConeDev::box_bounds_host(&w->k, norm ? sc.D.data() + w->cone.box_off : nullptr, hbl.data() + (size_t)k * nb, hbu.data() + (size_t)k * nb);
+    }
+    w->ls.set_multi_values(K, W, ax.data(), nzA, w->has_P ? px.data() : nullptr, nzP);
+    f.vD.upload(hD.data(), hD.size(), w->stream);
+    f.vE.upload(hE.data(), hE.size(), w->stream);
+    if (nb) {
+      f.vbl.upload(hbl.data(), hbl.size(), w->stream);
+      f.vbu.upload(hbu.data(), hbu.size(), w->stream);
+    }
+    HIP_CHECK(hipStreamSynchronize(w->stream)); // the host blocks end here; the call returns with the stream idle
+    f.vcols = K;
+    f.vlayout = W;
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(w->stream);
+    if (w->fam) w->fam->free_values(); // the workspace stays usable, with no values set
+    w->ls.free_multi_values();
+    return family_values_refuse(w, "scs_amd_family_set_values: HIP error or failed allocation: no values are set");
+  }
+  return 0;
+}
+
+static scs_int family_values_solve(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                   const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  const char *name = "scs_amd_solve_family_values";
+  if (!w || !B || !Cc || !sols || !infos)
+    return family_values_refuse(w, "scs_amd_solve_family_values: missing ScsWork, B, Cc, ScsSolution or ScsInfo input");
+  w->values_arg_refusal = nullptr;
+  if (const char *why = family_refusal(w, true)) {
+    printf("ERROR: %s\n", why);
+    return SCS_FAILED;
+  }
+  if (nprob < 1 || nprob > MULTI_W_MAX) return family_values_refuse(w, "scs_amd_solve_family_values: nprob must be 1 .. 16 (set and solve in groups)");
+  if ((long long)ldb < (long long)w->m || (long long)ldc < (long long)w->n) return family_values_refuse(w, "scs_amd_solve_family_values: ldb < m or ldc < n");
+  if (scales)
+    for (scs_int k = 0; k < nprob; ++k)
+      if (!std::isfinite((double)scales[k]) || !(scales[k] > 0))
+        return family_values_refuse(w, "scs_amd_solve_family_values: every one of the scales must be a positive finite number");
+  if (w->stale) return family_values_refuse(w, "scs_amd_solve_family_values: the last scs_amd_update_matrix failed: update again before solving");
+  const FamilyWork *fv = w->fam;
+  if (!fv || fv->vcols == 0 || !w->ls.multi || w->ls.multi->vcols != fv->vcols)
+    return family_values_refuse(w, "scs_amd_solve_family_values: no values are set (scs_amd_family_set_values)");
+  if (fv->vcols != (int)nprob) return family_values_refuse(w, "scs_amd_solve_family_values: nprob differs from the set call's");
+  InterruptListener listener;
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    if (w->stgs.verbose) print_header(w);
+    (void)family_chunk<true, true>(w, (int)nprob, fv->vlayout, B, (size_t)ldb, Cc, (size_t)ldc, scales, sols, infos, warm_start);
+    if (w->stgs.verbose) print_rule();
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
+    const std::string msg = std::string("HIP error in ") + name;
+    for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, msg.c_str(), "failure");
+    return SCS_FAILED;
+  }
+  return 0;
+}
+
 extern "C" {
+
+scs_int scs_amd_family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+  return family_set_values(w, nprob, AX, ldax, PX, ldpx);
+}
+
+scs_int scs_amd_solve_family_values(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  return family_values_solve(w, nprob, B, ldb, Cc, ldc, scales, sols, infos, warm_start);
+}
+
+void scs_amd_family_free_values(ScsWork *w) {
+  if (!w) return;
+  (void)hipSetDevice(w->device);
+  (void)hipStreamSynchronize(w->stream);
+  if (w->fam) w->fam->free_values();
+  w->ls.free_multi_values();
+}
+
+// host only: the normalised bounds scs_init and the set call keep for a box cone whose rows are scaled by Db (bsize values; NULL:
+// the bounds as given, the normalize == 0 case) -- bl / bu receive bsize - 1 values each
+scs_int scs_amd_box_bounds(const ScsCone *k, const scs_float *Db, scs_float *bl, scs_float *bu) {
+  if (!k || k->bsize < 1 || (k->bsize > 1 && (!k->bl || !k->bu || !bl || !bu))) return -1;
+  ConeDev::box_bounds_host(k, Db, bl, bu);
+  return 0;
+}
+
+// the setting the two entries refuse, else the arguments the last call of either was refused for (until a call is accepted)
+const char *scs_amd_solve_family_values_refusal(const ScsWork *w) {
+  if (!w) return nullptr;
+  if (const char *why = family_refusal(w, true)) return why;
+  return w->values_arg_refusal;
+}
 
 const char *scs_amd_solve_family_stream_refusal(const ScsWork *w, scs_int own_scale) {
   if (!w) return nullptr;

@@ -77,6 +77,11 @@ inline void hip_check(hipError_t e, const char *what, const char *file, int line
     default: throw HipError("scs_amd: bad block width");                                                               \
     }                                                                                                                  \
   } while (0)
+// a runtime flag as the constant FLAG (the PERCOL / DCOL / VCOL template arguments)
+#define MULTI_FLAG(flag_, FLAG, CALL)                                                                                  \
+  do {                                                                                                                 \
+    if (flag_) { constexpr bool FLAG = true; CALL; } else { constexpr bool FLAG = false; CALL; }                       \
+  } while (0)
 
 // one zero-fill stream per host thread, owned by a thread_local holder: destroyed when the thread
 // exits and when the thread switches device

@@ -71,6 +71,8 @@ struct ConeDev {
 
   void init(const ScsCone *k, int m, const real *D_host, hipStream_t s);
   void upload_box_bounds(const ScsCone *k, const real *D_host); // bl / bu (allocated) from the cone's bounds and D
+  // the host half of it: hl / hu (bsize - 1 each) from the cone's bounds and the box rows Db of D (bsize values; null: as given)
+  static void box_bounds_host(const ScsCone *k, const real *Db, real *hl, real *hu);
   void update_scaling(const ScsCone *k, const real *D_host);    // a new D on the same cone: bounds again, every warm start as after init
   // cw (device, length m) <- Proj_K(cw), projection under the diag(r_y)^-1 metric
   // (only the box cone looks at r_y; nullptr = Euclidean).
@@ -85,13 +87,16 @@ struct ConeDev {
   void proj_dual_multi(real *X, int W, int K, const real *r_y);
   // the same without the Moreau wrapper: Proj_K per column.  own_ry: every column under its own r_y (only the box cone reads it),
   // column k's slice of the copy that set_multi_ry keeps; r_y is then not read
-  void proj_primal_multi(real *X, int W, int K, const real *r_y, bool own_ry = false);
+  // bl_cols / bu_cols (both or neither): every column under its own normalised box bounds (its own D), column k's bsize - 1 values at
+  // k * (bsize - 1); null: the cone's own bl / bu in every column
+  void proj_primal_multi(real *X, int W, int K, const real *r_y, bool own_ry = false, const real *bl_cols = nullptr,
+                         const real *bu_cols = nullptr);
   // keeps a column-major copy of the box rows of the m x W block Ry; to be called again when Ry changes
   void set_multi_ry(const real *Ry, int W);
   void reset_multi_cold();                                       // box Newton starts and eigenbases of the block state: cold
   void reset_multi_box_start(int k);                             // the per-column half of it: column position k's box Newton start
   // launches shared by the two paths
-  void launch_box(real *tx, real *t_warm, const real *rb);
+  void launch_box(real *tx, real *t_warm, const real *rb, const real *lo = nullptr, const real *hi = nullptr); // lo / hi null: bl / bu
   void launch_psd_lds(real *cw, int nblocks, const int *off, const int *kk, real *tscratch, real *vprev, int warm);
   int rows() const { return m; }
 };

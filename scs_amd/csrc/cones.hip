@@ -979,10 +979,8 @@ static inline int small_grid(long long len) {
 // normalize_box_cone (cones.c:1161-1177) applied to a private copy.  The reference only calls it when a
 // scaling exists (cones.c:1561: `if (scal)`), so without one the bounds are used exactly as given -- a
 // "1e20 = infinite" bound then stays the finite number 1e20, as in the reference
-void ConeDev::upload_box_bounds(const ScsCone *k, const real *D) {
-  std::vector<real> hl(bsize - 1), hu(bsize - 1);
-  const real *Db = D ? D + box_off : nullptr;
-  for (int j = 0; j < bsize - 1; ++j) {
+void ConeDev::box_bounds_host(const ScsCone *k, const real *Db, real *hl, real *hu) {
+  for (int j = 0; j < (int)k->bsize - 1; ++j) {
     if (!Db) {
       hu[j] = k->bu[j];
       hl[j] = k->bl[j];
@@ -992,6 +990,10 @@ void ConeDev::upload_box_bounds(const ScsCone *k, const real *D) {
     hu[j] = k->bu[j] >= (real)MAX_BOX_VAL ? (real)INFINITY : k->bu[j] * f;
     hl[j] = k->bl[j] <= (real)-MAX_BOX_VAL ? (real)-INFINITY : k->bl[j] * f;
   }
+}
+void ConeDev::upload_box_bounds(const ScsCone *k, const real *D) {
+  std::vector<real> hl(bsize - 1), hu(bsize - 1);
+  box_bounds_host(k, D ? D + box_off : nullptr, hl.data(), hu.data());
   bl.upload(hl.data(), bsize - 1, stream);
   bu.upload(hu.data(), bsize - 1, stream);
   HIP_CHECK(hipStreamSynchronize(stream));
@@ -1132,15 +1134,16 @@ void ConeDev::init(const ScsCone *k, int m_, const real *D, hipStream_t s) {
 }
 
 // tx: the box cone's rows [t; x] of one vector; t_warm: its Newton start, read and updated
-void ConeDev::launch_box(real *tx, real *t_warm, const real *rb) {
+void ConeDev::launch_box(real *tx, real *t_warm, const real *rb, const real *lo, const real *hi) {
+  if (!lo) lo = bl.p, hi = bu.p;
   if (box_multi) {
     const int g = std::max(1, std::min(BOX_MULTI_GRID, (bsize - 1 + 8 * SCSAMD_BLOCK - 1) / (8 * SCSAMD_BLOCK)));
     BoxCtl *ctl = reinterpret_cast<BoxCtl *>(box_ctl.p);
     for (int it = 0; it <= BOX_MAX_ITERS; ++it)
-      hipLaunchKernelGGL(k_box_step, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, tx, bl.p, bu.p, bsize, t_warm, rb, ctl, box_part.p, it);
-    hipLaunchKernelGGL(k_box_apply, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, tx, bl.p, bu.p, bsize, t_warm, ctl);
+      hipLaunchKernelGGL(k_box_step, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, tx, lo, hi, bsize, t_warm, rb, ctl, box_part.p, it);
+    hipLaunchKernelGGL(k_box_apply, dim3(g), dim3(SCSAMD_BLOCK), 0, stream, tx, lo, hi, bsize, t_warm, ctl);
   } else {
-    hipLaunchKernelGGL(k_box, dim3(1), dim3(BOX_THREADS), 0, stream, tx, bl.p, bu.p, bsize, t_warm, rb);
+    hipLaunchKernelGGL(k_box, dim3(1), dim3(BOX_THREADS), 0, stream, tx, lo, hi, bsize, t_warm, rb);
   }
 }
 

@@ -362,7 +362,7 @@ void ConeDev::set_multi_ry(const real *Ry, int W) {
 // X (device, m x W block) <- Proj_K of its columns (proj_cone, cones.c:1340-1394, per column), without the Moreau wrapper: what
 // proj_primal is to proj_dual.  The elementwise and second-order passes run over all W columns; the box cone and the PSD blocks beyond
 // the LDS path over columns 0 .. K - 1.  Padding columns that hold zeros keep them.
-void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y, bool own_ry) {
+void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y, bool own_ry, const real *bl_cols, const real *bu_cols) {
   ensure_multi(W);
   ConeMulti &mc = *multi;
   if (own_ry && bsize > 0 && !mc.ry_cols.p) throw HipError("scs_amd: per-column r_y of the box cone has not been set");
@@ -372,8 +372,10 @@ void ConeDev::proj_primal_multi(real *X, int W, int K, const real *r_y, bool own
     const int gb = std::max(1, std::min(2048, (bsize + CONE_TR - 1) / CONE_TR));
     MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_rows_to_cols<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
     const real *rb = r_y ? r_y + box_off : (const real *)nullptr;
+    const size_t nb = bsize > 1 ? (size_t)bsize - 1 : 0; // a column's bounds
     for (int k = 0; k < K; ++k)
-      launch_box(mc.cols.p + (size_t)k * m + box_off, mc.box_t.p + k, own_ry ? mc.ry_cols.p + (size_t)k * m + box_off : rb);
+      launch_box(mc.cols.p + (size_t)k * m + box_off, mc.box_t.p + k, own_ry ? mc.ry_cols.p + (size_t)k * m + box_off : rb,
+                 bl_cols ? bl_cols + k * nb : nullptr, bl_cols ? bu_cols + k * nb : nullptr);
     MULTI_DISPATCH(W, hipLaunchKernelGGL(k_m_cols_to_rows<MW>, dim3(gb), dim3(SCSAMD_BLOCK), 0, stream, X, mc.cols.p, m, box_off, box_off + bsize));
   }
   if (n_tiny)

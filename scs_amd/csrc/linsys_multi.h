@@ -368,12 +368,6 @@ static void launch_spmm_epi(int epi, const SpmmArgs &a) {
   default: throw HipError("scs_amd: bad block-product epilogue");
   }
 }
-// a runtime flag as the constant FLAG (the PERCOL / DCOL / VCOL template arguments)
-#define MULTI_FLAG(flag_, FLAG, CALL)                                                                                  \
-  do {                                                                                                                 \
-    if (flag_) { constexpr bool FLAG = true; CALL; } else { constexpr bool FLAG = false; CALL; }                       \
-  } while (0)
-
 void LinSys::launch_spmm(int W, int epi, const CsrDev &mat, const real *X, real *Y, const EpiArgs &e, const int *cskip, const int *allskip,
                          bool dcol, const real *vals) {
   SpmmArgs a{spmm_grid(mat.rows, W), stream, mat.view(), X, Y, e, cskip, allskip, vals, (eoff)mat.bias};

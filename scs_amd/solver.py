@@ -105,7 +105,48 @@ class SCS:
                                                px.ctypes.data_as(T.fp) if px is not None else None) != 0:
                 raise RuntimeError("scs_amd_update_matrix failed")
 
-    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None, scale=None, own_scale=False, stream=False, width=None):
+    def _values_blocks(self, A, P):
+        """A / P of set_family_values as the nnz x K blocks of the library: lists of K matrices on the construction pattern (or of K
+        value arrays in its CSC order), or nnz x K arrays.  The checks of update(A=, P=) per column; ValueError before any library call."""
+        has_P = self._prob.matP is not None
+        if A is None:
+            raise ValueError("A must be given: the values of every problem's A")
+        if (P is not None) != has_P:
+            raise ValueError("P must be given exactly when the object was built with a P")
+
+        def cols(V, which):
+            if isinstance(V, (list, tuple)):
+                if not V:
+                    raise ValueError(f"{which} must hold at least one problem's values")
+                V = np.column_stack([self._prob.values_of(M, which) for M in V])
+            nnz = len(self._prob.Ax) if which == "A" else len(self._prob.Px)
+            return capi.values_block(V, nnz, which, self._T.np_float)
+        AX = cols(A, "A")
+        PX = cols(P, "P") if has_P else None
+        if PX is not None and PX.shape[1] != AX.shape[1]:
+            raise ValueError("A and P must hold the same number of problems")
+        return AX, PX
+
+    def set_family_values(self, A, P=None):
+        """scs_amd_family_set_values: the values of K <= 16 problems' A (and P) on the pattern given at construction, stored for any
+        number of solve_family(B, C, own_values=True) calls.  A / P: lists of K scipy matrices with exactly that pattern, or nnz x K
+        arrays in its CSC order (P: upper triangle).  A different pattern or a non-finite value raises ValueError before the library
+        is called; a refusal of the library raises ValueError with its message.  The object's own problem is not touched."""
+        if not self._w:
+            raise RuntimeError("solver was closed")
+        AX, PX = self._values_blocks(A, P)
+        if capi.family_set_values(self._lib, self._w, AX, PX) != 0:
+            why = self._lib.scs_amd_solve_family_values_refusal(self._w)
+            raise ValueError(why.decode() if why else "scs_amd_family_set_values failed")
+        return AX.shape[1]
+
+    def free_family_values(self):
+        """scs_amd_family_free_values: releases what set_family_values holds on the device"""
+        if self._w:
+            capi.family_free_values(self._lib, self._w)
+
+    def solve_family(self, B, C, warm_start=False, x=None, y=None, s=None, scale=None, own_scale=False, stream=False, width=None,
+                     A=None, P=None, own_values=False):
         """scs_amd_solve_family: K problems that share A, P and the cones of this object and differ in (b, c), in one
         device-resident loop.  B: m x K, C: n x K, as arrays or as lists of K vectors.  With warm_start, x (n x K), y and
         s (m x K) seed the columns.  Returns a list of K dicts in the shape `solve` returns.  The object's own problem and
@@ -117,10 +158,20 @@ class SCS:
         stream=True (scs_amd_solve_family_stream): the K problems are a queue through one block of `width` columns (2, 4, 8 or
         16; None: chosen from K), a finished column's slot going to the next problem, instead of chunks of 16 that each wait
         for their slowest column; every problem has the bits the call without stream gives it at that width.  Cones with PSD
-        blocks are refused (ValueError with the library's message); a width that is none of those raises ValueError."""
+        blocks are refused (ValueError with the library's message); a width that is none of those raises ValueError.
+        A= (and P= when the object has a P; scs_amd_solve_family_values): problem k has its own matrix values as well, given as
+        for set_family_values, K <= 16; it runs under its own scale as with own_scale, and is what update(A=A[k], P=P[k], b=, c=)
+        and solve() would give.  own_values=True: the values of the last set_family_values instead (set once, solve many).
+        Neither goes with stream=True (ValueError)."""
         if not self._w:
             raise RuntimeError("solver was closed")
         m, n = self._prob.m, self._prob.n
+        values = A is not None or P is not None or bool(own_values)
+        if values and stream:
+            raise ValueError("A / P / own_values do not go with stream=True: the stream entry shares the values of A and P")
+        if own_values and (A is not None or P is not None):
+            raise ValueError("own_values=True uses the values of set_family_values: give no A / P")
+        vblocks = self._values_blocks(A, P) if values and not own_values else None
 
         def block(v, rows, what):
             if isinstance(v, (list, tuple)):
@@ -147,7 +198,9 @@ class SCS:
             scale = np.asarray(scale, dtype=float).reshape(-1)
             if scale.shape[0] != K:
                 raise ValueError("scale must hold one initial scale per problem")
-        if not stream:
+        if vblocks is not None and vblocks[0].shape[1] != K:
+            raise ValueError("A must hold one matrix per column of B")
+        if not stream and not values:
             why = (self._lib.scs_amd_solve_family_scaled_refusal if scaled else self._lib.scs_amd_solve_family_refusal)(self._w)
             if why:
                 raise ValueError(why.decode())
@@ -158,6 +211,18 @@ class SCS:
             warm = (block(x, n, "x"), block(y, m, "y"), block(s, m, "s"))
             if any(v.shape[1] != K for v in warm):
                 raise ValueError("warm-start blocks must have K columns")
+        if values:
+            # the refusal function of these two entries reports the last call's arguments too: asked after a call that failed
+            rc = capi.family_set_values(self._lib, self._w, *vblocks) if vblocks is not None else 0
+            out = None
+            if rc == 0:
+                rc, out = capi.solve_family_values(self._lib, self._w, B, C_, scales=scale, warm=warm)
+            if rc != 0:
+                why = self._lib.scs_amd_solve_family_values_refusal(self._w)
+                if why:
+                    raise ValueError(why.decode())
+                raise RuntimeError("scs_amd_solve_family_values failed")
+            return out
         if stream:
             rc, out = capi.solve_family_stream(self._lib, self._w, B, C_, width=int(width), own_scale=scaled, scales=scale, warm=warm)
         elif scaled:
