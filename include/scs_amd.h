@@ -632,6 +632,56 @@ scs_int scs_amd_plan_reorder_entries(const ScsMatrix *A, const ScsCone *k, scs_i
  * (src/scs.c:745-762): a logged reference run follows a tighter schedule than an unlogged one, and this puts
  * the solve on that schedule without writing a log (bench.py times the CPU window's schedule with it). */
 void scs_amd_set_residuals_every_iter(ScsWork *w, scs_int on);
+/* ---- a batch of SMALL problems that share A, P, the cone and the settings: one workgroup per problem, one launch ----
+ * The contract of scs_amd_solve_family -- problem p is scs_update(w, B[:,p], Cc[:,p]); scs_solve(...) on a workspace with
+ * adaptive_scale = 0 and acceleration_lookback = 0 -- for problems small enough that a problem's whole state fits in one
+ * workgroup's LDS, for ANY nprob >= 1, and with EXACT linear solves: the scale is fixed, so H = R_x + P + A' R_y^-1 A (n x n,
+ * dense) is factored once at init and applied as a dense inverse with one step of refinement (scs_amd/csrc/small_batch.h).  A
+ * workgroup runs a problem from its first iteration to its convergence test (every 25 iterations; solved, infeasible, unbounded,
+ * or max_iters with the "inaccurate" statuses) inside one kernel and then takes the next problem from a counter; the host is
+ * not involved until the launch has ended.  A batch may mix all of these outcomes.  Equilibration (done once, at init, by the
+ * host passes of scs_init), normalize_b_c per problem, the feasible first iteration, the normalisation of v, root_plus, alpha,
+ * rho_x, scale, the residuals, the three tests, `iter` and the warm start are the reference's (src/scs.c).
+ * Bits: every reduction has a fixed order and the only atomic is the integer problem counter, so a problem's (x, y, s) and
+ * ScsInfo depend neither on nprob, on its index, on its neighbours, on the grid nor on the run.  They are not the bits of
+ * scs_solve (exact against iterative solves: the iteration counts differ too).
+ * scs_amd_small_init: d, k, stgs as scs_init takes them (d->b and d->c must be present and are not used).  Served: cones z, l and
+ * q of any sizes (1 and 2 included), P present or absent, normalize 0 or 1, any scale, rho_x, alpha, eps_*, max_iters; sizes up
+ * to scs_amd_small_limits: out[0] = the largest n, out[1] = the largest n + m + 1.  Not served, and named in the refusal: box,
+ * PSD, complex PSD, exponential and power cones; adaptive_scale, acceleration_lookback and time_limit_secs != 0;
+ * log_csv_filename and write_data_filename; a size over a limit; a NULL argument; non-finite values in A or P; a problem
+ * scs_init's validation rejects; a reduced matrix that is not positive definite (an indefinite P).  A refused init returns NULL;
+ * scs_amd_small_refusal returns the message of the last refused init / solve of the calling thread, NULL when that thread's last
+ * init / solve was not refused.  Init is host work only (equilibration, H and its factor, the padded rows); the device side of
+ * the object is created by its first accepted solve, so every refusal -- of init and of solve -- comes before any device call,
+ * and a machine without a device shows in that solve (SCS_FAILED, the failure convention below).
+ * scs_amd_small_solve: B, ldb, Cc, ldc, sols, infos, warm_start as in scs_amd_solve_family; sols[p].x / y / s must be allocated
+ * by the caller.  Refused with SCS_FAILED before any device call, sols / infos untouched: a NULL argument (a NULL sols[p].x / y /
+ * s included), nprob < 1, ldb < m or ldc < n, non-finite values in B or Cc.  Returns 0 otherwise; infos[p].status_val is the
+ * problem's own status.  infos[p].solve_time is the wall time of the launch the problem ran in (at most 32768 problems per
+ * launch), lin_sys_time, cone_time and the acceleration fields are 0, scale_updates is 0.  verbose: one summary row per problem
+ * after its launch, as scs_amd_solve_family_stream prints them; no header.
+ * A HIP failure fails every problem of the call (NaN-filled, SCS_FAILED, message on stderr) and leaves the object usable.  A
+ * SIGINT is honoured BETWEEN LAUNCHES ONLY: a launch that has started runs to its end (at most max_iters iterations per problem);
+ * the problems of the launches not yet started get SCS_SIGINT.
+ * scs_amd_small_set_grid: the number of workgroups of the following launches (0: the default, what the chip holds at once:
+ * CUs x workgroups per CU by the kernel's LDS; never more than the problems of the launch); returns 0, or -1 on a bad argument.
+ * scs_amd_small_get_counters, summed over the object's life: out[0] launches, out[1] workgroups launched, out[2] problems,
+ * out[3] iterations (the sum of infos[p].iter).  scs_amd_small_get_occupancy: out[0] workgroups per CU, out[1] LDS bytes per
+ * workgroup, out[2] the default grid, out[3] the setup time of init in microseconds.
+ * Memory: the padded rows of A and A', three dense n x n matrices, and per problem of the largest launch 2 (n + 2 m) + 27 values
+ * (+ n + m + 1 once a call has warm-started), in HBM; 6 (n + m + 1) + 2 m + 3 n + 264 values of LDS per workgroup.
+ * One caller thread per object; several GPUs are not used. */
+typedef struct ScsAmdSmall ScsAmdSmall;
+ScsAmdSmall *scs_amd_small_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
+const char *scs_amd_small_refusal(void);
+void scs_amd_small_limits(scs_int out[2]);
+scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                            ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
+scs_int scs_amd_small_set_grid(ScsAmdSmall *s, scs_int workgroups);
+void scs_amd_small_get_counters(const ScsAmdSmall *s, long long out[4]);
+void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[4]);
+void scs_amd_small_finish(ScsAmdSmall *s);
 /* ---- B1', drop-in form: the reference's internal cone interface -------------------
  * The nine symbols of include/cones.h:80-90 (prefix `_scs_` = glbopts.h's SCS(x)), exported
  * by libscsamd_cones.so so that a reference build links it IN PLACE OF src/cones.o (the

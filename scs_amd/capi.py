@@ -305,6 +305,24 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_get_spmv_kernel_name.argtypes = [C.c_void_p, scs_int, C.c_char_p, scs_int]
             lib.scs_amd_set_residuals_every_iter.restype = None
             lib.scs_amd_set_residuals_every_iter.argtypes = [C.c_void_p, scs_int]
+            # a batch of small problems, one workgroup per problem (include/scs_amd.h; scs_amd/small.py is the object form)
+            lib.scs_amd_small_init.restype = C.c_void_p
+            lib.scs_amd_small_init.argtypes = [C.POINTER(T.ScsData), C.POINTER(T.ScsCone), C.POINTER(T.ScsSettings)]
+            lib.scs_amd_small_refusal.restype = C.c_char_p
+            lib.scs_amd_small_refusal.argtypes = []
+            lib.scs_amd_small_limits.restype = None
+            lib.scs_amd_small_limits.argtypes = [C.POINTER(scs_int * 2)]
+            lib.scs_amd_small_solve.restype = scs_int
+            lib.scs_amd_small_solve.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, C.POINTER(T.ScsSolution),
+                                                C.POINTER(T.ScsInfo), scs_int]
+            lib.scs_amd_small_set_grid.restype = scs_int
+            lib.scs_amd_small_set_grid.argtypes = [C.c_void_p, scs_int]
+            lib.scs_amd_small_get_counters.restype = None
+            lib.scs_amd_small_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
+            lib.scs_amd_small_get_occupancy.restype = None
+            lib.scs_amd_small_get_occupancy.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
+            lib.scs_amd_small_finish.restype = None
+            lib.scs_amd_small_finish.argtypes = [C.c_void_p]
     lib._scs_types = T
     return lib
 

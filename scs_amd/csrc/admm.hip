@@ -1796,3 +1796,4 @@ void scs_amd_get_stats(const ScsWork *cw, ScsAmdStats *out) {
 } // extern "C"
 
 #include "admm_multi.h" // families of problems: K solves in one loop on blocks
+#include "small_batch.h" // batches of small problems: one workgroup solves a problem from start to end in one kernel

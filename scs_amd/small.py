@@ -1,0 +1,151 @@
+"""`SmallBatch` -- any number of SMALL problems that share A, P, the cone and the settings and differ in (b, c), every problem
+solved from its first iteration to its convergence test by one workgroup inside one kernel (scs_amd_small_* in include/scs_amd.h).
+
+    with SmallBatch(data, cone, eps_abs=1e-4, eps_rel=1e-4) as sb:
+        results = sb.solve(B, C)            # B: m x K, C: n x K  ->  K dicts with 'x', 'y', 's', 'info'
+
+data, cone, settings: the construction arguments of `scs_amd.solver.SCS`.  adaptive_scale and acceleration_lookback default to 0
+here (the batch serves nothing else); what the library does not serve -- box, PSD, exponential and power cones, a size over
+`.limits`, adaptive scale, acceleration, a time limit, the two file names -- raises ValueError with the library's message.
+Host code only: every flop is in libscsamd.so.
+"""
+import ctypes as ct
+
+import numpy as np
+
+from . import capi
+
+_IGNORED = {"use_indirect", "gpu", "mkl", "linear_solver"}
+
+
+def limits(lib=None):
+    """(largest n, largest n + m + 1) the library serves"""
+    lib = lib or capi.load("libscsamd.so")
+    out = (lib._scs_types.scs_int * 2)()
+    lib.scs_amd_small_limits(ct.byref(out))
+    return int(out[0]), int(out[1])
+
+
+class SmallBatch:
+    def __init__(self, data, cone, dtype="f64", **settings):
+        self._lib = capi.load("libscsamd_f32.so" if dtype in ("f32", np.float32) else "libscsamd.so")
+        self._T = self._lib._scs_types
+        self._h = None
+        if any(k not in data for k in ("A", "b", "c")):
+            raise ValueError("data must contain 'A', 'b' and 'c'")
+        cone = dict(cone)
+        if "f" in cone:
+            cone["z"] = cone.pop("f") + cone.get("z", 0)
+        for k in ("q", "s", "cs", "p", "bu", "bl"):
+            if k in cone and np.isscalar(cone[k]):
+                cone[k] = [cone[k]]
+        self._prob = capi.Problem(data["A"], data["b"], data["c"], cone, P=data.get("P"), T=self._T)
+        kw = {k: v for k, v in settings.items() if k not in _IGNORED}
+        for k in ("write_data_filename", "log_csv_filename"):
+            if isinstance(kw.get(k), str):
+                kw[k] = kw[k].encode()
+        kw.setdefault("verbose", 0)
+        kw.setdefault("adaptive_scale", 0)
+        kw.setdefault("acceleration_lookback", 0)
+        self._settings = capi.default_settings(self._lib, **kw)
+        self.limits = limits(self._lib)
+        self._h = self._lib.scs_amd_small_init(ct.byref(self._prob.data), ct.byref(self._prob.k), ct.byref(self._settings))
+        if not self._h:
+            why = self._lib.scs_amd_small_refusal()
+            raise ValueError("scs_amd_small_init: " + (why.decode() if why else "failed (no HIP device, or a HIP error: see stderr)"))
+
+    @property
+    def n(self):
+        return self._prob.n
+
+    @property
+    def m(self):
+        return self._prob.m
+
+    def solve(self, B, C, warm=None):
+        """B: m x K, C: n x K (anything numpy turns into 2-D arrays of finite numbers; a 1-D array is one problem).  warm: (X, Y, S)
+        of shapes n x K, m x K, m x K, the warm start of every problem, or None.  Returns K dicts(x, y, s, info).  ValueError on a
+        wrong shape, a non-numeric dtype, non-finite values, or whatever the library refuses (with its message); RuntimeError when
+        the call failed on the device."""
+        if not self._h:
+            raise RuntimeError("batch was closed")
+        T, f = self._T, self._T.np_float
+        n, m = self._prob.n, self._prob.m
+        try:
+            B = np.asarray(B, dtype=f)
+            Cc = np.asarray(C, dtype=f)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"B and C must be numeric arrays: {e}") from None
+        if B.ndim == 1 and Cc.ndim == 1:
+            B, Cc = B[:, None], Cc[:, None]
+        if B.ndim != 2 or Cc.ndim != 2 or B.shape[0] != m or Cc.shape[0] != n or B.shape[1] != Cc.shape[1] or B.shape[1] < 1:
+            raise ValueError(f"B must be m x K = {m} x K and C n x K = {n} x K with the same K >= 1")
+        if not (np.all(np.isfinite(B)) and np.all(np.isfinite(Cc))):
+            raise ValueError("B and C must be finite")
+        B, Cc = np.asfortranarray(B), np.asfortranarray(Cc)
+        K = B.shape[1]
+        X, Y, S = (np.zeros((n, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"))
+        if warm is not None:
+            if len(warm) != 3:
+                raise ValueError("warm must be (X, Y, S)")
+            for dst, src, nm in ((X, warm[0], "X"), (Y, warm[1], "Y"), (S, warm[2], "S")):
+                src = np.asarray(src, dtype=f)
+                if src.ndim == 1:
+                    src = src[:, None]
+                if src.shape != dst.shape:
+                    raise ValueError(f"warm {nm} must have shape {dst.shape}")
+                dst[:] = src
+        sols = (T.ScsSolution * K)()
+        infos = (T.ScsInfo * K)()
+        sz = np.dtype(f).itemsize
+        for k in range(K):
+            sols[k].x = ct.cast(X.ctypes.data + k * n * sz, T.fp)
+            sols[k].y = ct.cast(Y.ctypes.data + k * m * sz, T.fp)
+            sols[k].s = ct.cast(S.ctypes.data + k * m * sz, T.fp)
+        rc = self._lib.scs_amd_small_solve(self._h, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos,
+                                           1 if warm is not None else 0)
+        if rc != 0:
+            why = self._lib.scs_amd_small_refusal()
+            if why:
+                raise ValueError("scs_amd_small_solve: " + why.decode())
+            raise RuntimeError("scs_amd_small_solve failed on the device (see stderr)")
+        return [dict(x=X[:, k].copy(), y=Y[:, k].copy(), s=S[:, k].copy(), info=capi.info_dict(infos[k])) for k in range(K)]
+
+    def set_grid(self, workgroups):
+        """the number of workgroups of the following launches; 0: the default (what the chip holds at once)"""
+        if not self._h:
+            raise RuntimeError("batch was closed")
+        if isinstance(workgroups, bool) or not isinstance(workgroups, (int, np.integer)) or \
+                self._lib.scs_amd_small_set_grid(self._h, int(workgroups)) != 0:
+            raise ValueError("workgroups must be an integer in 0 .. 1048576")
+
+    def counters(self):
+        """summed over the object's life: launches, workgroups, problems, iterations"""
+        out = (ct.c_longlong * 4)()
+        if self._h:
+            self._lib.scs_amd_small_get_counters(self._h, ct.byref(out))
+        return dict(zip(("launches", "workgroups", "problems", "iterations"), (int(v) for v in out)))
+
+    def occupancy(self):
+        """workgroups per CU, LDS bytes per workgroup, the default grid, and the setup time in seconds"""
+        out = (ct.c_longlong * 4)()
+        if self._h:
+            self._lib.scs_amd_small_get_occupancy(self._h, ct.byref(out))
+        return dict(wg_per_cu=int(out[0]), lds_bytes=int(out[1]), default_grid=int(out[2]), setup_s=int(out[3]) / 1e6)
+
+    def close(self):
+        if self._h:
+            self._lib.scs_amd_small_finish(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
