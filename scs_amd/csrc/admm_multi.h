@@ -20,7 +20,12 @@
 // block products (cskip of csr_block_kernel) and the block solve (pre_stopped of MultiRhs), and its slot of the cone block is
 // scratch.  Padding columns k >= K are frozen from the start and hold zeros.
 //
-// Two entries, one loop.  scs_amd_solve_family: the columns share the workspace's diag_r (the instantiations with PERCOL / PC =
+// Two entries, one loop.  The loop is, on the device, the glue kernels below, each stated once with its forms as template flags, and,
+// on the host, family_iterate -- the one place that launches an iteration -- with family_begin (the state of a loop, FamLoop),
+// family_scale_due / family_rescale (update_scale) and family_fetch_ry / family_warm (the warm start) around it; the form of a call is
+// a runtime value (FamForm) that becomes the kernels' flags where they are launched.  family_chunk and family_stream_run keep only what
+// differs on purpose: how columns are loaded and returned, and when a column ends.
+// scs_amd_solve_family: the columns share the workspace's diag_r (the instantiations with PERCOL = false, FamForm::own_r =
 // false).  scs_amd_solve_family_scaled: column k runs under its own diag_r_k, built from its own scale, in an l x W block R whose x
 // and y rows are the rx / ry blocks of the per-column block solve (MultiOp::rx / ry / Minv, linsys.h); the glue kernels read
 // R[f] where the shared form reads R[f / W], in the same expressions, so equal scales give the shared form's bits.  With
@@ -67,8 +72,8 @@
 // A fourth entry, the scaled loop for problems that share the pattern and the cones but not the VALUES of A and P.
 // scs_amd_family_set_values runs scs_init's value-dependent half once per column (scs_amd_update_matrix's code on scratch copies: the
 // internal numbering, the equilibration, D_k / E_k, the box cone's bounds) and stores the equilibrated values in the linear system's
-// value blocks; scs_amd_solve_family_values is family_chunk<true, true>, where the products, the preconditioner, D / E in the
-// residuals, the Scaling of the host steps and the box bounds are the column's own (VC, DCOL).  Column k is, bit for bit, column k of
+// value blocks; scs_amd_solve_family_values is family_chunk in the form {own_r, own_vals}, where the products, the preconditioner, D / E
+// in the residuals, the Scaling of the host steps and the box bounds are the column's own (DCOL).  Column k is, bit for bit, column k of
 // the scaled entry on a workspace brought to values k by scs_amd_update_matrix.  At most 16 problems, no stream form.
 #pragma once
 
@@ -443,8 +448,9 @@ __global__ __launch_bounds__(SCSAMD_BLOCK) void k_f_resid_final(const real *part
 // ============================================================================
 // host control: solve_begin / solve_steps / populate_residuals / has_converged / finalize per column
 // ============================================================================
-// Family state: belongs to scs_amd_solve_family only.  Blocks at the largest width used so far (a narrower chunk uses the front
-// of each buffer at its own width), allocated at the first call, freed with the workspace.
+// Family state: what the family entries keep on a workspace, and nothing else reads.  Blocks at the largest width used so far (a
+// narrower chunk uses the front of each buffer at its own width), allocated at the first call of any entry, freed with the workspace;
+// the parts that only one form needs are allocated at that form's first call (below).
 struct FamilyWork {
   int width = 0;
   DevBuf<real> u, u_t, v, rsk; // l x W iterates
@@ -724,46 +730,201 @@ static void family_update_g(ScsWork *w, int W, int K, bool own_r, const int *ski
   w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
 }
 
-// K (1 <= K <= W) problems as one block of width W.  B / Cc: column-major host data of this chunk.  Returns SCS_SIGINT when
-// interrupted (the unfinished columns are then filled by fail_out), 0 otherwise; throws on a HIP failure.
-// PC = false: scs_amd_solve_family, the columns share the workspace's diag_r.  PC = true: scs_amd_solve_family_scaled, column k
+// ---- the form of a call, and what every entry hands to the loops after its own checks ----------------------------------------
+// own_r = false: scs_amd_solve_family, the columns share the workspace's diag_r.  own_r = true: scs_amd_solve_family_scaled, column k
 // runs under its own diag_r_k from scales[k] (null: the workspace's stgs.scale in every column) and, with adaptive_scale, under its
 // own update_scale; the workspace's diag_r and the linear system's rx / ry / M are not read.
-// VC (with PC only): scs_amd_solve_family_values, column k under its own A_k and P_k as well -- the blocks of the set call in force
-// (FamilyWork::vD ..., the linear system's value blocks) stand where the shared form reads the workspace's values, D, E, scal and box
-// bounds, which are then not read.
-template <bool PC, bool VC = false>
-static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, const real *Cc, size_t ldc, const real *scales,
-                        ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
-  const int n = w->n, m = w->m, l = w->l;
-  hipStream_t st = w->stream;
-  const size_t nw = (size_t)n * W, mw = (size_t)m * W, lw = (size_t)l * W;
+// own_vals (with own_r only): scs_amd_solve_family_values, column k under its own A_k and P_k as well -- the blocks of the set call in
+// force (FamilyWork::vD ..., the linear system's value blocks) stand where the shared form reads the workspace's values, D, E, scal
+// and box bounds, which are then not read.
+// The kernels' PERCOL / DCOL arguments are these flags, made constants where a kernel is launched (MULTI_FLAG).
+struct FamForm {
+  bool own_r, own_vals;
+};
+
+struct FamCall {
+  FamForm form;
+  scs_int nprob;
+  const real *B, *Cc; // column-major host data, problem p at B + p * ldb / Cc + p * ldc
+  size_t ldb, ldc;
+  const real *scales; // own_r: the problems' initial scales, or null
+  ScsSolution *sols;
+  ScsInfo *infos;
+  scs_int warm_start;
+  int stream; // scs_amd_solve_family_stream: the width of its block; 0: the call is cut into chunks
+  int width;  // of every chunk (scs_amd_solve_family_values: the set call's layout); 0: chosen from the chunk's size
+};
+
+// ---- THE ONE LOOP: family_begin, family_iterate, family_scale_due / family_rescale, family_ry ---------------------------------
+// What a chunk and a stream have in common, built once per chunk or stream by family_begin.
+struct FamLoop {
+  ScsWork *w;
+  int W, K; // the block's width; columns in use (K .. W - 1 are padding: frozen and zero throughout)
+  FamForm form;
+  bool phased, adapt; // the stream: every column its own local iteration; the columns run update_scale
+  const real *R;      // own_r: the l x W block; else the workspace's vector of l
+  int gl, gnm;        // grids over l x W and (n + m) x W
+  real *part, *nrm_part, *warm_part;
+  const int *frozen; // FamCtl::frozen on the device
+  FamCol cols[MULTI_W_MAX];
+  double t_lin = 0;
+  std::vector<real> hr; // R_y on the host, for the warm starts (family_ry)
+};
+
+static void family_begin(FamLoop &c, ScsWork *w, int W, int K, FamForm form, bool stream) {
   family_ensure(w, W);
-  if (PC) family_ensure_r(w, W);
+  if (form.own_r) family_ensure_r(w, W);
+  if (stream) family_ensure_stream(w, W);
   w->ls.ensure_multi(W);
   w->cone.ensure_multi(W);
   w->cone.reset_multi_cold(); // every family solve starts its eigenbases and box Newton starts cold: reruns are bit-identical
   FamilyWork &f = *w->fam;
-  const real *const R = PC ? f.R.p : w->diag_r.p; // l x W block / one vector of l
-  const int gl = glue_grid((long long)l * W), gnm = glue_grid((long long)(n + m) * W);
-  const double t0 = now_ms();
-  double t_lin = 0;
+  c.w = w, c.W = W, c.K = K, c.form = form, c.phased = stream;
+  c.adapt = form.own_r && w->stgs.adaptive_scale;
+  c.R = form.own_r ? f.R.p : w->diag_r.p;
+  c.gl = glue_grid((long long)w->l * W), c.gnm = glue_grid((long long)(w->n + w->m) * W);
+  c.part = f.part.p, c.nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, c.warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
+  c.frozen = f.ctl.p->frozen;
   w->cone_timer.total_ms = 0;
   w->cone_timer.samples = 0;
-  FamCol cols[MULTI_W_MAX];
+}
+
+// One iteration of src/scs.c:1356-1455 on the block, from the norm of v to the Moreau post of the cone step; true at a check
+// (i % CONVERGED_INTERVAL == 0: v is then left to the caller's dual update).  i: the global iteration; column k stands at its local
+// iteration i - cols[k].start.  What the loop derives from the iteration index -- the feasible first iteration, the normalisation
+// of v, the warm-start term of the CG tolerance -- it derives per column: in a stream (phased) as masks of columns and one factor per
+// column, in a chunk, whose columns all stand at i, in the scalar form of the same kernels.
+static bool family_iterate(FamLoop &c, int i) {
+  ScsWork *w = c.w;
+  FamilyWork &f = *w->fam;
+  const int W = c.W, K = c.K, n = w->n, m = w->m, l = w->l, gl = c.gl, gnm = c.gnm;
+  const real *const R = c.R;
+  hipStream_t st = w->stream;
+  int first = 0, norm = 0; // bit k: column k runs its feasible first iteration / normalises v
+  real tolv[MULTI_W_MAX], wsc[MULTI_W_MAX];
+  for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = 0, wsc[k] = 1;
+  for (int k = 0; k < K; ++k) {
+    if (w->cg_tol_override > 0) tolv[k] = (real)w->cg_tol_override;
+    if (c.cols[k].frozen) continue;
+    const int j = i - c.cols[k].start;
+    (j < FEASIBLE_ITERS ? first : norm) |= 1 << k;
+    if (w->cg_tol_override > 0) continue;
+    tolv[k] = std::min(c.cols[k].r_n.nm_ax_s_btau, c.cols[k].r_n.nm_px_aty_ctau); // its own tolerance schedule (:745-762)
+    wsc[k] = (real)1.0 / std::pow((real)j + 1, (real)CG_RATE);
+  }
+  if (!c.phased) first = first != 0, norm = norm != 0; // one iteration for all: do_normalize / feasible_iter as the single loop has them
+  if (norm) MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, c.nrm_part, f.ctl.p));
+  MULTI_DISPATCH(W, MULTI_FLAG(c.form.own_r, PERCOL, MULTI_FLAG(c.phased, PHASED,
+                    hipLaunchKernelGGL((k_f_prep_linsys<MW, PERCOL, PHASED>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
+                                       f.warm.p, n, l, c.nrm_part, gl, c.warm_part, norm, f.ctl.p))));
+  { // the linear system (:763)
+    const double tl = now_ms();
+    MultiRhs a(f.u_t.p, f.u_t.p + (size_t)n * W, f.warm.p, family_op(w, W, c.form.own_r, c.form.own_vals));
+    a.pre_stopped = c.frozen;
+    if (!(w->cg_tol_override > 0)) {
+      a.warm_part = c.warm_part;
+      a.warm_cnt = gl;
+      if (c.phased) a.warm_scale_col = wsc;
+      else a.warm_scale = (real)1.0 / std::pow((real)i + 1, (real)CG_RATE);
+    }
+    w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
+    c.t_lin += now_ms() - tl;
+  }
+  if (norm)
+    MULTI_DISPATCH(W, MULTI_FLAG(c.form.own_r, PERCOL,
+                      hipLaunchKernelGGL((k_f_root_plus_partial<MW, PERCOL>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
+                                         n + m, c.part, PSTRIDE, f.ctl.p)));
+  MULTI_DISPATCH(W, MULTI_FLAG(c.form.own_r, PERCOL, MULTI_FLAG(c.phased, PHASED,
+                    hipLaunchKernelGGL((k_f_post_linsys<MW, PERCOL, PHASED>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
+                                       f.cw.p, n, l, c.part, gnm, PSTRIDE, first, f.ctl.p))));
+  int cslot = -1;
+  if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
+  if (c.form.own_vals) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true, f.vbl.p, f.vbu.p); // and between the column's own bounds
+  else if (c.form.own_r) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true); // the box cone under the column's own r_y
+  else w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
+  w->cone_timer.stop(cslot, st);
+  w->cone_projs++;
+  const bool check = i % CONVERGED_INTERVAL == 0; // a stream's starts are multiples of CONVERGED_INTERVAL: all columns check together
+  MULTI_DISPATCH(W, MULTI_FLAG(c.form.own_r, PERCOL,
+                    hipLaunchKernelGGL((k_f_post_cone<MW, PERCOL>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
+                                       f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p)));
+  return check;
+}
+
+// update_scale's host half for a running column at its local iteration j (admm.hip, :1164-1241): true when its scale has changed --
+// the next control record then names the column in FamCtl::upd
+static bool family_scale_due(FamCol &c, int j) {
+  real new_scale;
+  if (!scale_update_due(c.r_o, c.nm_b_orig, c.nm_c_orig, c.scale, j, c.sum_log_scale_factor, c.n_log_scale_factor, c.last_scale_update_iter,
+                        &new_scale))
+    return false;
+  c.scale_updates++;
+  c.scale = new_scale;
+  return c.upd = true;
+}
+
+// update_scale's device half for the columns in upd, after the control record that names them; of the others not one bit changes
+static void family_rescale(FamLoop &c) {
+  ScsWork *w = c.w;
+  FamilyWork &f = *w->fam;
+  family_apply_scales(w, c.W, c.K, c.form.own_vals);
+  family_update_g(w, c.W, c.K, c.form.own_r, f.ctl.p->keep, c.form.own_vals);
+  MULTI_DISPATCH(c.W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(c.gl), dim3(SCSAMD_BLOCK), 0, w->stream, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p,
+                                         w->l, f.ctl.p));
+  for (int k = 0; k < c.K; ++k) c.cols[k].upd = false;
+}
+
+// The host copy of R_y for the warm starts, after columns have been set: the R block, downloaded every time (the new columns' rows
+// have just been written), or the shared diag_r, downloaded once per loop
+static void family_fetch_ry(FamLoop &c) {
+  ScsWork *w = c.w;
+  if (!c.form.own_r && !c.hr.empty()) return;
+  const size_t lw = (size_t)w->l * c.W;
+  c.hr.resize(c.form.own_r ? lw : (size_t)w->l);
+  if (c.form.own_r) w->fam->R.download(c.hr.data(), lw, w->stream); // element (i, k) at i * W + k
+  else w->diag_r.download(c.hr.data(), w->l, w->stream);
+  HIP_CHECK(hipStreamSynchronize(w->stream));
+}
+
+// solve_begin's warm start of column k from sol, under the column's own R_y (family_stage_warm)
+static bool family_warm(FamLoop &c, int k, const ScsSolution &sol) {
+  ScsWork *w = c.w;
+  const real *ry = c.form.own_r ? c.hr.data() + (size_t)w->n * c.W + k : c.hr.data() + w->n;
+  return family_stage_warm(w, c.form.own_vals ? w->fam->vscal[k] : w->scal, sol, c.cols[k], ry, c.form.own_r ? c.W : 1);
+}
+
+static scs_int family_fail_all(ScsWork *w, scs_int nprob, ScsSolution *sols, ScsInfo *infos, scs_int status_val, const char *msg,
+                               const char *status) {
+  for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], status_val, msg, status);
+  return status_val;
+}
+
+// Problems off .. off + K - 1 of the call (1 <= K <= W) as one block of width W.  Returns SCS_SIGINT when interrupted (the
+// unfinished columns are then filled by fail_out), 0 otherwise; throws on a HIP failure.
+static int family_chunk(ScsWork *w, int K, int W, const FamCall &q, scs_int off) {
+  const int n = w->n, m = w->m, l = w->l;
+  hipStream_t st = w->stream;
+  const size_t nw = (size_t)n * W, mw = (size_t)m * W, lw = (size_t)l * W;
+  const bool PC = q.form.own_r, VC = q.form.own_vals;
+  FamLoop c;
+  family_begin(c, w, W, K, q.form, false);
+  FamilyWork &f = *w->fam;
+  FamCol *cols = c.cols;
+  ScsSolution *sols = q.sols + off;
+  const double t0 = now_ms();
 
   // ---- scs_update per column (:1287-1325): renumber, norms of the data as given, normalize_b_c with the column's own sigma
   f.hblk.assign(mw, (real)0);
   f.hblk2.assign(nw, (real)0);
   for (int k = 0; k < K; ++k) {
-    family_stage_data(w, VC ? f.vscal[k] : w->scal, B + (size_t)k * ldb, Cc + (size_t)k * ldc, cols[k]);
+    family_stage_data(w, VC ? f.vscal[k] : w->scal, q.B + (size_t)(off + k) * q.ldb, q.Cc + (size_t)(off + k) * q.ldc, cols[k]);
     for (int i = 0; i < m; ++i) f.hblk[(size_t)i * W + k] = f.col_y[i];
     for (int j = 0; j < n; ++j) f.hblk2[(size_t)j * W + k] = f.col_x[j];
   }
   f.b.upload(f.hblk.data(), mw, st);
   f.c.upload(f.hblk2.data(), nw, st);
   for (int k = 0; k < K; ++k) {
-    cols[k].scale = PC && scales ? scales[k] : w->stgs.scale;
+    cols[k].scale = PC && q.scales ? q.scales[off + k] : w->stgs.scale;
     cols[k].upd = PC;
   }
   family_upload_ctl(w, W, K, cols, PC ? 1 : 0);
@@ -773,13 +934,10 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
 
   // ---- solve_begin per column: warm / cold start (:660-687)
   f.hblk.assign(lw, (real)0);
-  if (warm_start) {
-    std::vector<real> hr(PC ? lw : (size_t)l); // PC: the R block, element (i, k) at i * W + k
-    if (PC) f.R.download(hr.data(), lw, st);
-    else w->diag_r.download(hr.data(), l, st);
-    HIP_CHECK(hipStreamSynchronize(st));
+  if (q.warm_start) {
+    family_fetch_ry(c);
     for (int k = 0; k < K; ++k) {
-      if (!family_stage_warm(w, VC ? f.vscal[k] : w->scal, sols[k], cols[k], PC ? hr.data() + (size_t)n * W + k : hr.data() + n, PC ? W : 1)) continue; // its own R_y
+      if (!family_warm(c, k, sols[k])) continue;
       for (int j = 0; j < n; ++j) f.hblk[(size_t)j * W + k] = f.col_x[j];
       for (int i = 0; i < m; ++i) f.hblk[(size_t)(n + i) * W + k] = f.col_y[i];
     }
@@ -794,52 +952,14 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   HIP_CHECK(hipStreamSynchronize(st));
 
   // ---- update_work_cache per column: g = (R + M)^-1 [c; -b] to CG_BEST_TOL (:1118-1128)
-  const int *frozen = f.ctl.p->frozen;
-  real tolv[MULTI_W_MAX];
-  family_update_g(w, W, K, PC, frozen, VC);
+  family_update_g(w, W, K, PC, c.frozen, VC);
 
   // ---- the loop of src/scs.c:1356-1455 on blocks
-  real *part = f.part.p, *nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, *warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
   const int max_iters = (int)w->stgs.max_iters;
   int time_limit_reached = 0, running = K, i = 0;
   bool sigint = false;
   for (; i < max_iters && running > 0; ++i) {
-    const int do_norm = i >= FEASIBLE_ITERS;
-    if (do_norm) MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
-                                         f.warm.p, n, l, nrm_part, gl, warm_part, do_norm, f.ctl.p));
-    { // the linear system (:763), every column on its own tolerance schedule (:745-762)
-      const double tl = now_ms();
-      MultiRhs a(f.u_t.p, f.u_t.p + nw, f.warm.p, family_op(w, W, PC, VC));
-      a.pre_stopped = frozen;
-      if (w->cg_tol_override > 0) {
-        for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
-      } else {
-        for (int k = 0; k < K; ++k) tolv[k] = std::min(cols[k].r_n.nm_ax_s_btau, cols[k].r_n.nm_px_aty_ctau);
-        a.warm_part = warm_part;
-        a.warm_cnt = gl;
-        a.warm_scale = (real)1.0 / std::pow((real)i + 1, (real)CG_RATE);
-      }
-      w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
-      t_lin += now_ms() - tl;
-    }
-    const int feas = i < FEASIBLE_ITERS;
-    if (!feas)
-      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
-                                           n + m, part, PSTRIDE, f.ctl.p));
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
-                                         f.cw.p, n, l, part, gnm, PSTRIDE, feas, f.ctl.p));
-    int cslot = -1;
-    if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
-    if (VC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true, f.vbl.p, f.vbu.p); // and between the column's own bounds
-    else if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true); // the box cone under the column's own r_y
-    else w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
-    w->cone_timer.stop(cslot, st);
-    w->cone_projs++;
-    const bool check = i % CONVERGED_INTERVAL == 0;
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
-                                         f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
-    if (!check) continue;
+    if (!family_iterate(c, i)) continue;
     if (interrupted()) { // :1400-1403
       sigint = true;
       break;
@@ -861,30 +981,16 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
     const bool timed_out = w->stgs.time_limit_secs && now_ms() - t0 > 1000. * w->stgs.time_limit_secs;
     // update_scale per running column, where the single loop runs it: after the convergence test, before the dual update (:1410-1412)
     bool rescaled = false;
-    if (PC && w->stgs.adaptive_scale && !timed_out)
-      for (int k = 0; k < K; ++k) {
-        FamCol &c = cols[k];
-        if (c.frozen) continue;
-        real new_scale;
-        if (scale_update_due(c.r_o, c.nm_b_orig, c.nm_c_orig, c.scale, i, c.sum_log_scale_factor, c.n_log_scale_factor,
-                             c.last_scale_update_iter, &new_scale)) {
-          c.scale_updates++;
-          c.scale = new_scale;
-          c.upd = rescaled = true;
-        }
-      }
+    if (c.adapt && !timed_out)
+      for (int k = 0; k < K; ++k)
+        if (!cols[k].frozen && family_scale_due(cols[k], i)) rescaled = true;
     if (changed || rescaled) family_upload_ctl(w, W, K, cols); // one record: the pinned copy is rewritten after the next wait only
     if (timed_out) {
       time_limit_reached = 1;
       break;
     }
-    if (rescaled) { // update_scale's device half for the columns in upd; of the others not one bit changes
-      family_apply_scales(w, W, K, VC);
-      family_update_g(w, W, K, PC, f.ctl.p->keep, VC);
-      MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
-      for (int k = 0; k < K; ++k) cols[k].upd = false;
-    }
-    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
+    if (rescaled) family_rescale(c);
+    MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(c.gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
                                          f.ctl.p));
   }
   HIP_CHECK(hipStreamSynchronize(st));
@@ -909,10 +1015,9 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
   const double solve_ms = now_ms() - t0;
   const double cone_ms = w->cone_timer.samples ? w->cone_timer.total_ms * ((double)std::max(i, 1) / (double)w->cone_timer.samples) : 0.0;
   for (int k = 0; k < K; ++k) {
-    ScsSolution *sol = &sols[k];
-    ScsInfo *info = &infos[k];
+    ScsInfo *info = &q.infos[off + k];
     if (sigint && !cols[k].frozen) {
-      fail_out(w, m, n, sol, info, SCS_SIGINT, "interrupted", "interrupted");
+      fail_out(w, m, n, &sols[k], info, SCS_SIGINT, "interrupted", "interrupted");
       continue;
     }
     real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
@@ -921,63 +1026,9 @@ static int family_chunk(ScsWork *w, int K, int W, const real *B, size_t ldb, con
       y[r] = f.hblk[(size_t)(n + r) * W + k];
       s[r] = f.hblk2[(size_t)r * W + k];
     }
-    family_return(w, VC ? f.vscal[k] : w->scal, cols[k], PC, time_limit_reached, solve_ms, t_lin, cone_ms, sol, info);
+    family_return(w, VC ? f.vscal[k] : w->scal, cols[k], PC, time_limit_reached, solve_ms, c.t_lin, cone_ms, &sols[k], info);
   }
   return sigint ? SCS_SIGINT : 0;
-}
-
-// the body of the two entries.  PC / scales: as in family_chunk; `name`: the entry, for the messages
-template <bool PC>
-static scs_int family_solve(const char *name, ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
-                            const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
-  if (!w || !B || !Cc || !sols || !infos || nprob < 1) {
-    printf("ERROR: %s: missing ScsWork, B, Cc, ScsSolution or ScsInfo input, or nprob < 1\n", name);
-    return SCS_FAILED;
-  }
-  if ((long long)ldb < (long long)w->m || (long long)ldc < (long long)w->n) {
-    printf("ERROR: %s: ldb < m or ldc < n\n", name);
-    return SCS_FAILED;
-  }
-  if (const char *why = family_refusal(w, PC)) {
-    printf("ERROR: %s\n", why);
-    return SCS_FAILED;
-  }
-  if (PC && scales)
-    for (scs_int k = 0; k < nprob; ++k)
-      if (!std::isfinite((double)scales[k]) || !(scales[k] > 0)) {
-        printf("ERROR: %s: scales[%li] must be a positive finite number\n", name, (long)k);
-        return SCS_FAILED;
-      }
-  if (w->stale) { // the last scs_amd_update_matrix failed half way
-    for (scs_int k = 0; k < nprob; ++k)
-      fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
-    return SCS_FAILED;
-  }
-  InterruptListener listener;
-  scs_int done = 0; // columns already returned
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    if (w->stgs.verbose) print_header(w);
-    bool sigint = false;
-    for (; done < nprob; done += MULTI_W_MAX) { // chunks of at most 16 problems
-      const int K = (int)std::min<scs_int>(MULTI_W_MAX, nprob - done);
-      if (sigint) {
-        for (int k = 0; k < K; ++k) fail_out(w, w->m, w->n, &sols[done + k], &infos[done + k], SCS_SIGINT, "interrupted", "interrupted");
-        continue;
-      }
-      const int W = std::max(2, multi_width(K)); // one problem runs as a block of width 2: it stays off the single-solve state
-      sigint = family_chunk<PC>(w, K, W, B + (size_t)done * (size_t)ldb, (size_t)ldb, Cc + (size_t)done * (size_t)ldc, (size_t)ldc,
-                                PC && scales ? scales + done : nullptr, sols + done, infos + done, warm_start) == SCS_SIGINT;
-    }
-    if (w->stgs.verbose) print_rule();
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
-    const std::string msg = std::string("HIP error in ") + name;
-    for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, msg.c_str(), "failure");
-    return SCS_FAILED;
-  }
-  return 0;
 }
 
 // ============================================================================
@@ -991,39 +1042,27 @@ static const char *family_stream_refusal(const ScsWork *w, bool own_scale) {
   return nullptr;
 }
 
-// The loop.  returned[p] != 0: problem p has its result in sols[p] / infos[p].  Throws on a HIP failure; true when interrupted
-// (the problems not yet returned are then left to the caller).
-template <bool PC>
-static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_t ldb, const real *Cc, size_t ldc, const real *scales,
-                              ScsSolution *sols, ScsInfo *infos, scs_int warm_start, std::vector<char> &returned) {
-  const int n = w->n, m = w->m, l = w->l;
+// The queue q through the q.stream slots of one block: the schedule around family_iterate.  returned[p] != 0: problem p has its
+// result in q.sols[p] / q.infos[p].  Throws on a HIP failure; true when interrupted (the problems not yet returned are then left to
+// the caller).
+static bool family_stream_run(ScsWork *w, const FamCall &q, std::vector<char> &returned) {
+  const int n = w->n, m = w->m, l = w->l, W = q.stream, nprob = (int)q.nprob;
   hipStream_t st = w->stream;
-  const size_t nw = (size_t)n * W, lw = (size_t)l * W;
-  const int K = std::min(W, nprob); // slots in use; columns K .. W - 1 are padding: frozen and zero throughout
-  family_ensure(w, W);
-  if (PC) family_ensure_r(w, W);
-  family_ensure_stream(w, W);
-  w->ls.ensure_multi(W);
-  w->cone.ensure_multi(W);
-  w->cone.reset_multi_cold();
+  const bool PC = q.form.own_r;
+  const int K = std::min(W, nprob); // slots in use
+  FamLoop lp;
+  family_begin(lp, w, W, K, q.form, true);
   FamilyWork &f = *w->fam;
   long long *cnt = f.counters;
-  for (int q = 0; q < 6; ++q) cnt[q] = 0;
+  for (int t = 0; t < 6; ++t) cnt[t] = 0;
   cnt[5] = W;
-  const real *const R = PC ? f.R.p : w->diag_r.p;
-  const int gl = glue_grid((long long)l * W), gnm = glue_grid((long long)(n + m) * W);
-  w->cone_timer.total_ms = 0;
-  w->cone_timer.samples = 0;
+  const int gl = lp.gl, gnm = lp.gnm;
   const size_t rec_in = (size_t)m + n + l, rec_out = (size_t)n + 2 * (size_t)m;
   f.hstage.assign(rec_in * W, (real)0);
   f.hout.assign(rec_out * W, (real)0);
-  FamCol cols[MULTI_W_MAX];
-  for (FamCol &c : cols) c.frozen = true; // an empty slot
-  std::vector<real> hr;                   // R_y for the warm starts: the shared diag_r once, the R block at every warm fill
-  const int *frozen = f.ctl.p->frozen;
-  real tolv[MULTI_W_MAX], wsc[MULTI_W_MAX];
+  FamCol *cols = lp.cols;
+  for (int k = 0; k < MULTI_W_MAX; ++k) cols[k].frozen = true; // an empty slot
   const int max_iters = (int)w->stgs.max_iters;
-  double t_lin = 0;
   int next = 0, busy = 0, running = 0; // the queue's head; slots that hold a problem; slots whose column runs
 
   // The lowest free slots take the next problems of the queue, which start at global iteration `start`.  The stream is idle on
@@ -1037,8 +1076,8 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       c.start = start;
       c.frozen = c.pending = !first; // the first columns run from iteration 0: nothing to wait for
       c.upd = true;                  // its R (PC) and its g are built below, with every other column left as it is
-      c.scale = PC && scales ? scales[c.prob] : w->stgs.scale;
-      family_stage_data(w, w->scal, B + (size_t)c.prob * ldb, Cc + (size_t)c.prob * ldc, c);
+      c.scale = PC && q.scales ? q.scales[c.prob] : w->stgs.scale;
+      family_stage_data(w, w->scal, q.B + (size_t)c.prob * q.ldb, q.Cc + (size_t)c.prob * q.ldc, c);
       real *rec = f.hstage.data() + (size_t)k * rec_in;
       std::copy(f.col_y.begin(), f.col_y.end(), rec);
       std::copy(f.col_x.begin(), f.col_x.end(), rec + m);
@@ -1056,16 +1095,11 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
     if (!mask) return;
     family_upload_ctl(w, W, K, cols, first && PC ? 1 : 0);
     if (PC) family_apply_scales(w, W, K);
-    if (warm_start) { // solve_begin per problem, under its own R_y
-      if (PC || hr.empty()) {
-        hr.resize(PC ? lw : (size_t)l);
-        if (PC) f.R.download(hr.data(), lw, st);
-        else w->diag_r.download(hr.data(), l, st);
-        HIP_CHECK(hipStreamSynchronize(st));
-      }
+    if (q.warm_start) { // solve_begin per problem, under its own R_y
+      family_fetch_ry(lp);
       for (int k = 0; k < K; ++k) {
         if (!((mask >> k) & 1u)) continue;
-        if (!family_stage_warm(w, w->scal, sols[cols[k].prob], cols[k], PC ? hr.data() + nw + k : hr.data() + n, PC ? W : 1)) continue;
+        if (!family_warm(lp, k, q.sols[cols[k].prob])) continue;
         real *v = f.hstage.data() + (size_t)k * rec_in + m + n;
         std::copy(f.col_x.begin(), f.col_x.end(), v);
         std::copy(f.col_y.begin(), f.col_y.end(), v + n);
@@ -1076,7 +1110,7 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
                                                      hipMemcpyHostToDevice, st));
     MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_col_in<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.stage.p, mask, f.b.p, f.c.p, f.v.p, f.u.p,
                                          f.u_t.p, f.rsk.p, f.cw.p, f.warm.p, f.g.p, n, m));
-    family_update_g(w, W, K, PC, first ? frozen : f.ctl.p->keep); // update_work_cache for the new columns alone (:1118-1128)
+    family_update_g(w, W, K, PC, first ? lp.frozen : f.ctl.p->keep); // update_work_cache for the new columns alone (:1118-1128)
     for (int k = 0; k < K; ++k) cols[k].upd = false;
   };
 
@@ -1098,8 +1132,8 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
       std::copy(rec, rec + n, f.col_x.begin());
       std::copy(rec + n, rec + n + m, f.col_y.begin());
       std::copy(rec + n + m, rec + rec_out, f.col_s.begin());
-      family_return(w, w->scal, c, PC, c.time_limit_reached, t1 - c.t0, t_lin - c.t_lin0, cone_iter_ms * std::max(c.iter, 1), &sols[c.prob],
-                    &infos[c.prob]);
+      family_return(w, w->scal, c, PC, c.time_limit_reached, t1 - c.t0, lp.t_lin - c.t_lin0, cone_iter_ms * std::max(c.iter, 1),
+                    &q.sols[c.prob], &q.infos[c.prob]);
       returned[c.prob] = 1;
       c.prob = -1;
       --busy;
@@ -1107,7 +1141,6 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
   };
 
   fill(0, true);
-  real *part = f.part.p, *nrm_part = f.part.p + (size_t)8 * PSTRIDE * W, *warm_part = f.part.p + (size_t)9 * PSTRIDE * W;
   bool sigint = false;
   int i = 0, last = -1;
   for (;; ++i) {
@@ -1121,7 +1154,7 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
           if (!c.pending || c.start != i) continue;
           c.pending = c.frozen = false;
           c.t0 = now_ms();
-          c.t_lin0 = t_lin;
+          c.t_lin0 = lp.t_lin;
           w->cone.reset_multi_box_start(k); // the slot projected scratch while it waited
           ++running;
         }
@@ -1138,51 +1171,8 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
     }
     last = i;
     cnt[1] += running;
-    int first_mask = 0, norm_mask = 0; // per column what the chunk loop derives from i: here from j = i - start
-    for (int k = 0; k < K; ++k) {
-      if (cols[k].frozen) continue;
-      if (i - cols[k].start < FEASIBLE_ITERS) first_mask |= 1 << k;
-      else norm_mask |= 1 << k;
-    }
-    if (norm_mask) MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_sumsq_partial<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, l, nrm_part, f.ctl.p));
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_prep_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u_t.p, f.u.p, f.g.p, R,
-                                         f.warm.p, n, l, nrm_part, gl, warm_part, norm_mask, f.ctl.p));
-    {
-      const double tl = now_ms();
-      MultiRhs a(f.u_t.p, f.u_t.p + nw, f.warm.p, family_op(w, W, PC));
-      a.pre_stopped = frozen;
-      for (int k = 0; k < MULTI_W_MAX; ++k) tolv[k] = 0, wsc[k] = 1;
-      if (w->cg_tol_override > 0) {
-        for (int k = 0; k < K; ++k) tolv[k] = (real)w->cg_tol_override;
-      } else {
-        for (int k = 0; k < K; ++k) {
-          if (cols[k].frozen) continue;
-          tolv[k] = std::min(cols[k].r_n.nm_ax_s_btau, cols[k].r_n.nm_px_aty_ctau);
-          wsc[k] = (real)1.0 / std::pow((real)(i - cols[k].start) + 1, (real)CG_RATE);
-        }
-        a.warm_part = warm_part;
-        a.warm_cnt = gl;
-        a.warm_scale_col = wsc;
-      }
-      w->ls.solve_multi_blocks(K, W, a, tolv, nullptr);
-      t_lin += now_ms() - tl;
-    }
-    if (norm_mask)
-      MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_root_plus_partial<MW, PC>), dim3(gnm), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.v.p, f.g.p, R,
-                                           n + m, part, PSTRIDE, f.ctl.p));
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_linsys<MW, PC, true>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u_t.p, f.u.p, f.v.p, f.g.p, R,
-                                         f.cw.p, n, l, part, gnm, PSTRIDE, first_mask, f.ctl.p));
-    int cslot = -1;
-    if (w->cone_timer.used < 500) cslot = w->cone_timer.start(st);
-    if (PC) w->cone.proj_primal_multi(f.cw.p, W, K, nullptr, true);
-    else w->cone.proj_primal_multi(f.cw.p, W, K, w->diag_r.p + n);
-    w->cone_timer.stop(cslot, st);
-    w->cone_projs++;
-    const bool check = i % CONVERGED_INTERVAL == 0; // every start is a multiple of CONVERGED_INTERVAL: all columns check together
-    MULTI_DISPATCH(W, hipLaunchKernelGGL((k_f_post_cone<MW, PC>), dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.u.p, f.u_t.p, f.v.p, f.rsk.p, R,
-                                         f.cw.p, n, l, check ? (real)0 : w->stgs.alpha, f.ctl.p));
     unsigned ended = 0;
-    if (check) {
+    if (family_iterate(lp, i)) {
       if (interrupted()) {
         sigint = true;
         break;
@@ -1201,24 +1191,12 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
           c.iter = i - c.start;
           ended |= 1u << k;
           --running;
-          continue;
-        }
-        real new_scale;
-        if (PC && w->stgs.adaptive_scale &&
-            scale_update_due(c.r_o, c.nm_b_orig, c.nm_c_orig, c.scale, i - c.start, c.sum_log_scale_factor, c.n_log_scale_factor,
-                             c.last_scale_update_iter, &new_scale)) {
-          c.scale_updates++;
-          c.scale = new_scale;
-          c.upd = rescaled = true;
+        } else if (lp.adapt && family_scale_due(c, i - c.start)) {
+          rescaled = true;
         }
       }
       if (changed || rescaled) family_upload_ctl(w, W, K, cols); // the stream has been waited on and nothing has been enqueued since
-      if (rescaled) {
-        family_apply_scales(w, W, K);
-        family_update_g(w, W, K, PC, f.ctl.p->keep);
-        MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_remap_v<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.rsk.p, f.R.p, f.u_t.p, f.u.p, l, f.ctl.p));
-        for (int k = 0; k < K; ++k) cols[k].upd = false;
-      }
+      if (rescaled) family_rescale(lp);
       if (running > 0)
         MULTI_DISPATCH(W, hipLaunchKernelGGL(k_f_dual_update<MW>, dim3(gl), dim3(SCSAMD_BLOCK), 0, st, f.v.p, f.u.p, f.u_t.p, l, w->stgs.alpha,
                                              f.ctl.p));
@@ -1251,8 +1229,81 @@ static bool family_stream_run(ScsWork *w, int nprob, int W, const real *B, size_
   return sigint;
 }
 
-static scs_int family_stream_solve(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc, scs_int own_scale,
-                                   const scs_float *scales, scs_int width, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+// ============================================================================
+// the entries: every one its own checks, messages and record of a refusal, then family_run
+// ============================================================================
+// the first of the scales that is not a positive finite number, or -1 (none given: -1)
+static scs_int family_bad_scale(const scs_float *scales, scs_int nprob) {
+  for (scs_int k = 0; scales && k < nprob; ++k)
+    if (!std::isfinite((double)scales[k]) || !(scales[k] > 0)) return k;
+  return -1;
+}
+
+static scs_int family_fail_stale(ScsWork *w, const FamCall &q) { // the last scs_amd_update_matrix failed half way
+  return family_fail_all(w, q.nprob, q.sols, q.infos, SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
+}
+
+// A checked call of the entry `name`: the queue through a stream, or cut into chunks of at most 16 problems.  A HIP failure fails
+// every problem of the call; an interrupt fails the problems that have not been returned.
+static scs_int family_run(const char *name, ScsWork *w, const FamCall &q) {
+  InterruptListener listener;
+  std::vector<char> returned(q.stream ? (size_t)q.nprob : 0, 0);
+  try {
+    HIP_CHECK(hipSetDevice(w->device));
+    if (w->stgs.verbose) print_header(w);
+    if (q.stream) {
+      if (family_stream_run(w, q, returned)) {
+        (void)hipStreamSynchronize(w->stream);
+        for (scs_int k = 0; k < q.nprob; ++k)
+          if (!returned[k]) fail_out(w, w->m, w->n, &q.sols[k], &q.infos[k], SCS_SIGINT, "interrupted", "interrupted");
+      }
+    } else {
+      bool sigint = false;
+      for (scs_int done = 0; done < q.nprob; done += MULTI_W_MAX) { // done: problems already returned
+        const int K = (int)std::min<scs_int>(MULTI_W_MAX, q.nprob - done);
+        const int W = q.width ? q.width : std::max(2, multi_width(K)); // one problem runs as a block of width 2: it stays off the single-solve state
+        if (sigint) family_fail_all(w, K, q.sols + done, q.infos + done, SCS_SIGINT, "interrupted", "interrupted");
+        else sigint = family_chunk(w, K, W, q, done) == SCS_SIGINT;
+      }
+    }
+    if (w->stgs.verbose) print_rule();
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
+    const std::string msg = std::string("HIP error in ") + name;
+    return family_fail_all(w, q.nprob, q.sols, q.infos, SCS_FAILED, msg.c_str(), "failure");
+  }
+  return 0;
+}
+
+// the body of scs_amd_solve_family and scs_amd_solve_family_scaled; `name`: the entry, for the messages
+static scs_int family_solve(const char *name, bool own_r, ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc,
+                            scs_int ldc, const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  if (!w || !B || !Cc || !sols || !infos || nprob < 1) {
+    printf("ERROR: %s: missing ScsWork, B, Cc, ScsSolution or ScsInfo input, or nprob < 1\n", name);
+    return SCS_FAILED;
+  }
+  if ((long long)ldb < (long long)w->m || (long long)ldc < (long long)w->n) {
+    printf("ERROR: %s: ldb < m or ldc < n\n", name);
+    return SCS_FAILED;
+  }
+  if (const char *why = family_refusal(w, own_r)) {
+    printf("ERROR: %s\n", why);
+    return SCS_FAILED;
+  }
+  if (!own_r) scales = nullptr;
+  if (const scs_int k = family_bad_scale(scales, nprob); k >= 0) {
+    printf("ERROR: %s: scales[%li] must be a positive finite number\n", name, (long)k);
+    return SCS_FAILED;
+  }
+  const FamCall q{{own_r, false}, nprob, B, Cc, (size_t)ldb, (size_t)ldc, scales, sols, infos, warm_start, 0, 0};
+  if (w->stale) return family_fail_stale(w, q);
+  return family_run(name, w, q);
+}
+
+extern "C" scs_int scs_amd_solve_family_stream(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                               scs_int own_scale, const scs_float *scales, scs_int width, ScsSolution *sols, ScsInfo *infos,
+                                               scs_int warm_start) {
   const char *name = "scs_amd_solve_family_stream";
   if (!w || !B || !Cc || !sols || !infos || nprob < 1) {
     printf("ERROR: %s: missing ScsWork, B, Cc, ScsSolution or ScsInfo input, or nprob < 1\n", name);
@@ -1275,38 +1326,12 @@ static scs_int family_stream_solve(ScsWork *w, scs_int nprob, const scs_float *B
   }
   if (!own_scale && scales)
     return refuse("scs_amd_solve_family_stream: scales must be NULL with own_scale == 0: the problems then share the workspace's scale");
-  if (scales)
-    for (scs_int k = 0; k < nprob; ++k)
-      if (!std::isfinite((double)scales[k]) || !(scales[k] > 0))
-        return refuse("scs_amd_solve_family_stream: every one of the scales must be a positive finite number");
-  if (w->stale) { // the last scs_amd_update_matrix failed half way
-    for (scs_int k = 0; k < nprob; ++k)
-      fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, "the last scs_amd_update_matrix failed: update again before solving", "failure");
-    return SCS_FAILED;
-  }
-  if ((long long)nprob > 2147483647LL) return refuse("scs_amd_solve_family_stream: nprob exceeds 2^31 - 1");
+  if (family_bad_scale(scales, nprob) >= 0) return refuse("scs_amd_solve_family_stream: every one of the scales must be a positive finite number");
   const int W = width ? (int)width : std::max(2, multi_width(std::min<scs_int>(nprob, MULTI_W_MAX)));
-  InterruptListener listener;
-  std::vector<char> returned((size_t)nprob, 0);
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    if (w->stgs.verbose) print_header(w);
-    const bool sigint = own_scale ? family_stream_run<true>(w, (int)nprob, W, B, (size_t)ldb, Cc, (size_t)ldc, scales, sols, infos, warm_start, returned)
-                                  : family_stream_run<false>(w, (int)nprob, W, B, (size_t)ldb, Cc, (size_t)ldc, nullptr, sols, infos, warm_start, returned);
-    if (sigint) {
-      (void)hipStreamSynchronize(w->stream);
-      for (scs_int k = 0; k < nprob; ++k)
-        if (!returned[k]) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_SIGINT, "interrupted", "interrupted");
-    }
-    if (w->stgs.verbose) print_rule();
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
-    const std::string msg = std::string("HIP error in ") + name;
-    for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, msg.c_str(), "failure");
-    return SCS_FAILED;
-  }
-  return 0;
+  const FamCall q{{own_scale != 0, false}, nprob, B, Cc, (size_t)ldb, (size_t)ldc, scales, sols, infos, warm_start, W, 0};
+  if (w->stale) return family_fail_stale(w, q);
+  if ((long long)nprob > 2147483647LL) return refuse("scs_amd_solve_family_stream: nprob exceeds 2^31 - 1");
+  return family_run(name, w, q);
 }
 
 // ============================================================================
@@ -1314,8 +1339,8 @@ static scs_int family_stream_solve(ScsWork *w, scs_int nprob, const scs_float *B
 // ============================================================================
 // The set call is scs_init's value-dependent half per column, on scratch copies of the host matrices: values into the internal
 // numbering and equilibration exactly as scs_amd_update_matrix takes them, so column k's D_k, E_k and equilibrated values are, bit
-// for bit, those of a workspace brought to values k.  The solve call is family_chunk<true, true>: the loop of the scaled entry with
-// every input that follows the values -- the products, the preconditioner, D / E in the residuals, the Scaling of the host steps, the
+// for bit, those of a workspace brought to values k.  The solve call is one chunk in the form {own_r, own_vals}: the loop of the scaled
+// entry with every input that follows the values -- the products, the preconditioner, D / E in the residuals, the Scaling of the host steps, the
 // box cone's bounds -- taken from the column's own.  Nothing of the workspace's own problem is read for a column or written.
 static scs_int family_values_refuse(ScsWork *w, const char *why) {
   if (w) w->values_arg_refusal = why;
@@ -1323,7 +1348,7 @@ static scs_int family_values_refuse(ScsWork *w, const char *why) {
   return SCS_FAILED;
 }
 
-static scs_int family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+extern "C" scs_int scs_amd_family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
   if (!w || !AX) return family_values_refuse(w, "scs_amd_family_set_values: w and AX must be given");
   w->values_arg_refusal = nullptr;
   if (const char *why = family_refusal(w, true)) {
@@ -1406,9 +1431,10 @@ static scs_int family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX,
   return 0;
 }
 
-static scs_int family_values_solve(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
-                                   const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
-  const char *name = "scs_amd_solve_family_values";
+extern "C" {
+
+scs_int scs_amd_solve_family_values(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                    const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
   if (!w || !B || !Cc || !sols || !infos)
     return family_values_refuse(w, "scs_amd_solve_family_values: missing ScsWork, B, Cc, ScsSolution or ScsInfo input");
   w->values_arg_refusal = nullptr;
@@ -1418,40 +1444,15 @@ static scs_int family_values_solve(ScsWork *w, scs_int nprob, const scs_float *B
   }
   if (nprob < 1 || nprob > MULTI_W_MAX) return family_values_refuse(w, "scs_amd_solve_family_values: nprob must be 1 .. 16 (set and solve in groups)");
   if ((long long)ldb < (long long)w->m || (long long)ldc < (long long)w->n) return family_values_refuse(w, "scs_amd_solve_family_values: ldb < m or ldc < n");
-  if (scales)
-    for (scs_int k = 0; k < nprob; ++k)
-      if (!std::isfinite((double)scales[k]) || !(scales[k] > 0))
-        return family_values_refuse(w, "scs_amd_solve_family_values: every one of the scales must be a positive finite number");
+  if (family_bad_scale(scales, nprob) >= 0)
+    return family_values_refuse(w, "scs_amd_solve_family_values: every one of the scales must be a positive finite number");
   if (w->stale) return family_values_refuse(w, "scs_amd_solve_family_values: the last scs_amd_update_matrix failed: update again before solving");
   const FamilyWork *fv = w->fam;
   if (!fv || fv->vcols == 0 || !w->ls.multi || w->ls.multi->vcols != fv->vcols)
     return family_values_refuse(w, "scs_amd_solve_family_values: no values are set (scs_amd_family_set_values)");
   if (fv->vcols != (int)nprob) return family_values_refuse(w, "scs_amd_solve_family_values: nprob differs from the set call's");
-  InterruptListener listener;
-  try {
-    HIP_CHECK(hipSetDevice(w->device));
-    if (w->stgs.verbose) print_header(w);
-    (void)family_chunk<true, true>(w, (int)nprob, fv->vlayout, B, (size_t)ldb, Cc, (size_t)ldc, scales, sols, infos, warm_start);
-    if (w->stgs.verbose) print_rule();
-  } catch (const std::exception &ex) {
-    fprintf(stderr, "%s\n", ex.what());
-    (void)hipStreamSynchronize(w->stream); // nothing of this call may still be reading or writing
-    const std::string msg = std::string("HIP error in ") + name;
-    for (scs_int k = 0; k < nprob; ++k) fail_out(w, w->m, w->n, &sols[k], &infos[k], SCS_FAILED, msg.c_str(), "failure");
-    return SCS_FAILED;
-  }
-  return 0;
-}
-
-extern "C" {
-
-scs_int scs_amd_family_set_values(ScsWork *w, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
-  return family_set_values(w, nprob, AX, ldax, PX, ldpx);
-}
-
-scs_int scs_amd_solve_family_values(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
-                                    const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
-  return family_values_solve(w, nprob, B, ldb, Cc, ldc, scales, sols, infos, warm_start);
+  return family_run("scs_amd_solve_family_values", w,
+                    FamCall{{true, true}, nprob, B, Cc, (size_t)ldb, (size_t)ldc, scales, sols, infos, warm_start, 0, fv->vlayout});
 }
 
 void scs_amd_family_free_values(ScsWork *w) {
@@ -1483,12 +1484,6 @@ const char *scs_amd_solve_family_stream_refusal(const ScsWork *w, scs_int own_sc
   return w->stream_arg_refusal; // the arguments the last call was refused for, until a call is accepted
 }
 
-scs_int scs_amd_solve_family_stream(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
-                                    scs_int own_scale, const scs_float *scales, scs_int width, ScsSolution *sols, ScsInfo *infos,
-                                    scs_int warm_start) {
-  return family_stream_solve(w, nprob, B, ldb, Cc, ldc, own_scale, scales, width, sols, infos, warm_start);
-}
-
 void scs_amd_family_stream_get_counters(const ScsWork *w, long long out[6]) {
   for (int q = 0; q < 6; ++q) out[q] = w && w->fam ? w->fam->counters[q] : 0;
 }
@@ -1497,7 +1492,7 @@ const char *scs_amd_solve_family_refusal(const ScsWork *w) { return w ? family_r
 
 scs_int scs_amd_solve_family(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
                              ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
-  return family_solve<false>("scs_amd_solve_family", w, nprob, B, ldb, Cc, ldc, nullptr, sols, infos, warm_start);
+  return family_solve("scs_amd_solve_family", false, w, nprob, B, ldb, Cc, ldc, nullptr, sols, infos, warm_start);
 }
 
 // every column under its own scale, fixed (adaptive_scale == 0: a scale sweep) or adapted by its own update_scale
@@ -1505,7 +1500,7 @@ const char *scs_amd_solve_family_scaled_refusal(const ScsWork *w) { return w ? f
 
 scs_int scs_amd_solve_family_scaled(ScsWork *w, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
                                     const scs_float *scales, ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
-  return family_solve<true>("scs_amd_solve_family_scaled", w, nprob, B, ldb, Cc, ldc, scales, sols, infos, warm_start);
+  return family_solve("scs_amd_solve_family_scaled", true, w, nprob, B, ldb, Cc, ldc, scales, sols, infos, warm_start);
 }
 
 } // extern "C"
