@@ -20,9 +20,12 @@ namespace scsamd {
 static const double MIN_NORM_FACTOR = 1e-4, MAX_NORM_FACTOR = 1e4; // scs_matrix.c:13-14
 static const int NUM_RUIZ_PASSES = 25, NUM_L2_PASSES = 1;           // scs_matrix.c:15-16
 
+// The thresholds are double constants in the reference and the statistic is promoted to them, whatever scs_float is: in the
+// fp32 build a statistic of exactly (float)1e-4 -- which lies below 1e-4 -- is replaced by 1, where a comparison against the rounded
+// threshold would keep it.  1e4 is exact in both formats.
 static inline real limit_scale(real x) { // scs_matrix.c:229-234
-  x = x < (real)MIN_NORM_FACTOR ? (real)1.0 : x;
-  x = x > (real)MAX_NORM_FACTOR ? (real)MAX_NORM_FACTOR : x;
+  x = (double)x < MIN_NORM_FACTOR ? (real)1.0 : x;
+  x = (double)x > MAX_NORM_FACTOR ? (real)MAX_NORM_FACTOR : x;
   return x;
 }
 static inline real safe_div_pos(real x, real y) { // glbopts.h:194-196
@@ -154,8 +157,8 @@ real normalize_b_c_sigma(const Scaling &sc, real *b, real *c) {
     nb = std::max(nb, (real)std::fabs(b[i]));
   }
   real sigma = std::max(nc, nb);
-  sigma = sigma < (real)MIN_NORM_FACTOR ? (real)1 : sigma;
-  sigma = sigma > (real)MAX_NORM_FACTOR ? (real)MAX_NORM_FACTOR : sigma;
+  sigma = (double)sigma < MIN_NORM_FACTOR ? (real)1 : sigma; // promoted to the double threshold, as in limit_scale
+  sigma = (double)sigma > MAX_NORM_FACTOR ? (real)MAX_NORM_FACTOR : sigma;
   sigma = safe_div_pos((real)1, sigma);
   for (size_t j = 0; j < n; ++j) c[j] *= sigma;
   for (size_t i = 0; i < m; ++i) b[i] *= sigma;

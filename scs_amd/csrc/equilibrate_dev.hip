@@ -16,7 +16,8 @@
 // contraction off, max is order-free, and the one order-sensitive aggregate that has
 // no cheap ordered device form (the per-cone MEAN of the single L2 pass, up to ~1e5
 // rows summed serially) is done on the host between two kernels -- so the result is
-// bit-identical to equilibrate.cpp, which tests/test_equilibrate_gpu.py asserts.
+// bit-identical to equilibrate.cpp, which tests/test_equilibrate.py (random problems) and
+// tests/test_equilibrate_edges_gpu.py (the edge shapes of tests/equilibrate_cases.py, all three libraries) assert.
 #include "scs_host.h"
 #include <algorithm>
 
@@ -26,12 +27,13 @@ namespace scsamd {
 
 namespace {
 
-constexpr real MIN_NORM_FACTOR = (real)1e-4, MAX_NORM_FACTOR = (real)1e4;
+constexpr double MIN_NORM_FACTOR = 1e-4, MAX_NORM_FACTOR = 1e4;
 constexpr int SMALL_CONE = 64;
 
+// compared in double against the double thresholds, as the host does (equilibrate.cpp limit_scale): (float)1e-4 is below 1e-4
 __device__ __forceinline__ real d_limit_scale(real x) {
-  x = x < MIN_NORM_FACTOR ? (real)1.0 : x;
-  x = x > MAX_NORM_FACTOR ? MAX_NORM_FACTOR : x;
+  x = (double)x < MIN_NORM_FACTOR ? (real)1.0 : x;
+  x = (double)x > MAX_NORM_FACTOR ? (real)MAX_NORM_FACTOR : x;
   return x;
 }
 __device__ __forceinline__ real d_safe_div_pos(real x, real y) { return y < (real)1e-18 ? x / (real)1e-18 : x / y; }

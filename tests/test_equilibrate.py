@@ -46,6 +46,35 @@ def _equilibrate(lib, A, P, cone, where):
     return Ax, Px, D, E
 
 
+def _raw_matrix(T, m, n, p, i, x, keep):
+    """ScsMatrix of the type family T over raw CSC arrays (indices cast to T's scs_int, a private copy of the values in T's scs_float)"""
+    p, i = np.ascontiguousarray(p, dtype=T.np_int), np.ascontiguousarray(i, dtype=T.np_int)
+    x = np.array(x, dtype=T.np_float)
+    keep += [p, i, x]
+    return T.ScsMatrix(x.ctypes.data_as(T.fp), i.ctypes.data_as(T.ip), p.ctypes.data_as(T.ip), m, n), x
+
+
+def _equilibrate_raw(lib, m, n, A, P, cone, where):
+    """_equilibrate on raw CSC arrays, A = (Ap, Ai, Ax) and P = None or the same for its upper triangle, handed on as they are
+    (unsorted columns, duplicates, explicit zeros), for any of the product libraries in its own float and index types."""
+    T = lib._scs_types
+    keep = []
+    Am, Ax = _raw_matrix(T, m, n, *A, keep)
+    Pm, Px = None, None
+    if P is not None:
+        Pm, Px = _raw_matrix(T, n, n, *P, keep)
+    k = capi.make_cone(cone, T)
+    D, E = np.zeros(m, dtype=T.np_float), np.zeros(n, dtype=T.np_float)
+    lib.scs_amd_equilibrate.restype = T.scs_int
+    lib.scs_amd_equilibrate.argtypes = [C.POINTER(T.ScsMatrix), C.POINTER(T.ScsMatrix), C.POINTER(T.ScsCone), T.fp, T.fp,
+                                        T.scs_int]
+    rc = lib.scs_amd_equilibrate(C.byref(Am), C.byref(Pm) if Pm is not None else None, C.byref(k), D.ctypes.data_as(T.fp),
+                                 E.ctypes.data_as(T.fp), where)
+    assert rc == 0
+    del keep
+    return Ax, Px, D, E
+
+
 def test_host_equilibration_matches_reference_normalised_matrix():
     g = np.load(os.path.join(G, "linsys_cfg1.npz"))
     pr = problems.random_socp(1000, 3000, 32, seed=1234)
