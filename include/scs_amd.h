@@ -682,6 +682,37 @@ scs_int scs_amd_small_set_grid(ScsAmdSmall *s, scs_int workgroups);
 void scs_amd_small_get_counters(const ScsAmdSmall *s, long long out[4]);
 void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[4]);
 void scs_amd_small_finish(ScsAmdSmall *s);
+/* ---- the same batch with OWN VALUES of A and P per problem, on the pattern the object was built with ----
+ * scs_amd_small_set_values: AX is nnz(A) x nprob and PX nnz(upper P) x nprob (given exactly when the object was built with a P),
+ * column-major with leading dimensions ldax / ldpx, every column in the CSC order of the d->A / d->P handed to
+ * scs_amd_small_init, as for scs_amd_update_matrix; the pattern is the one of init, explicit zeros included.  Any nprob >= 1.
+ * Per problem the host checks the values, runs the equilibration of scs_init on them (normalize = 1; D = E = 1 otherwise), keeps
+ * D_p, E_p and writes the equilibrated values into the problem's blocks in HBM.  One set call serves any number of solve calls;
+ * a second set call replaces the values; scs_amd_small_free_values releases them (NULL-safe; scs_amd_small_finish does it too).
+ * scs_amd_small_solve_values: the arguments of scs_amd_small_solve; nprob is the set call's.  Problem p is
+ * scs_amd_small_init on (A_p, P_p) followed by scs_amd_small_solve of (b_p, c_p): the same iteration, equilibration,
+ * normalize_b_c, tests, statuses and warm start, launches of at most 32768 problems, and linear solves exact in the same sense.
+ * NOT BIT FOR BIT that pair: scs_amd_small_init factors H in long double on the host; here the problem's workgroup assembles
+ * H_p = R_x + P_p + A_p' R_y^-1 A_p, factors it (Cholesky) and inverts it in WORKING PRECISION on the device before the problem's
+ * first iteration, and the refinement step of every solve repairs what that loses.  The two agree in iter and status_val, and in
+ * ScsInfo and (x, y, s) to about 1e-6 relative (tests/test_small_values_gpu.py).  A problem's bits depend neither on nprob, on its
+ * index, on its neighbours, on the grid nor on the run: every sum of the factor is taken in an order the pattern fixes, without
+ * floating-point atomics.  scs_amd_small_solve stays usable on the same object before and after, with the bits it always had.
+ * Refused with SCS_FAILED before any device call, sols / infos untouched, the message in scs_amd_small_refusal: a NULL among s,
+ * AX, B, Cc, sols, infos or sols[p].x / y / s; PX given without a P, or missing with one; nprob < 1; ldax < nnz(A), ldpx < nnz(P),
+ * ldb < m or ldc < n; a non-finite value in AX, PX, B or Cc (the message names the problem); a solve before a set call, or with
+ * another nprob than the set call's.
+ * A problem whose H_p is not positive definite (an indefinite P_p) is found by the device factor's pivot test (> 0 and finite):
+ * that problem alone returns status_val = SCS_FAILED with NaN-filled x, y, s; the call returns 0 and its neighbours are untouched.
+ * A HIP failure or a failed allocation in the set call returns SCS_FAILED (message on stderr, no refusal) and leaves the object
+ * usable with no values set.
+ * Memory, in HBM: per problem of the set call m wA + n wAt values (wA, wAt: the longest row of A and of A'), n^2 for P when
+ * present, and m + n for D, E; per workgroup of the largest grid launched a slab of 2 n^2 values for the factor (it follows the
+ * grid, not nprob); the per-problem staging of scs_amd_small_solve.  On the host D_p, E_p (m + n values per problem). */
+scs_int scs_amd_small_set_values(ScsAmdSmall *s, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx);
+scs_int scs_amd_small_solve_values(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                   ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
+void scs_amd_small_free_values(ScsAmdSmall *s);
 /* ---- B1', drop-in form: the reference's internal cone interface -------------------
  * The nine symbols of include/cones.h:80-90 (prefix `_scs_` = glbopts.h's SCS(x)), exported
  * by libscsamd_cones.so so that a reference build links it IN PLACE OF src/cones.o (the

@@ -315,6 +315,12 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_small_solve.restype = scs_int
             lib.scs_amd_small_solve.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int, C.POINTER(T.ScsSolution),
                                                 C.POINTER(T.ScsInfo), scs_int]
+            lib.scs_amd_small_set_values.restype = scs_int
+            lib.scs_amd_small_set_values.argtypes = [C.c_void_p, scs_int, fp, scs_int, fp, scs_int]
+            lib.scs_amd_small_solve_values.restype = scs_int
+            lib.scs_amd_small_solve_values.argtypes = lib.scs_amd_small_solve.argtypes
+            lib.scs_amd_small_free_values.restype = None
+            lib.scs_amd_small_free_values.argtypes = [C.c_void_p]
             lib.scs_amd_small_set_grid.restype = scs_int
             lib.scs_amd_small_set_grid.argtypes = [C.c_void_p, scs_int]
             lib.scs_amd_small_get_counters.restype = None

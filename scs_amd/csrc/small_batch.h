@@ -18,8 +18,14 @@
 // sums over a fixed index range, combined by wave shuffles and a fixed loop over the four waves.  No floating-point atomics.  The
 // only atomic is the integer counter problems are taken from, so a problem's bits depend neither on the grid, on nprob, on its
 // index nor on its neighbours.  Every loop is bounded by max_iters, n, m, the row widths or the cone sizes.
+//
+// scs_amd_small_set_values / scs_amd_small_solve_values: the same batch with every problem's OWN values of A and P on the pattern
+// of init.  The host equilibrates every problem and writes its values into the problem's own padded rows and dense P; H is then
+// per problem, and the problem's workgroup assembles, factors and inverts it in working precision before the first iteration
+// (sb_factor, k_small_batch<true>).  k_small_batch<false> is the shared kernel, unchanged.
 #include <cstdarg>
 #include <memory>
+#include <type_traits>
 
 namespace scsamd {
 
@@ -39,6 +45,11 @@ struct SbArgs {
   real *xys, *q;                                // per problem: normalised x, y, s (n + 2 m); reduced scalars (SB_QS)
   int *it;                                      // per problem: iter, status_val
   int *counter;                                 // the next problem index
+};
+// own values (scs_amd_small_solve_values): Av, Atv, Pd, D, E hold one block per problem, at strides m wA, n wAt, n^2, m, n, and
+// Hinv is not read: every workgroup factors its problem's H into its own slab of 2 n^2 values (slab + 2 n^2 blockIdx.x)
+struct SbArgsOwn : SbArgs {
+  real *slab;
 };
 
 static size_t sb_lds_values(int n, int m) { return 6 * (size_t)(n + m + 1) + 2 * (size_t)m + 3 * (size_t)n + SB_BLOCK + 8; }
@@ -74,6 +85,77 @@ __device__ __forceinline__ void sb_mv(const real *__restrict__ val, const int *_
     }
     __syncthreads();
   }
+}
+
+// The per-problem factor of the own-values kernel, run by the problem's workgroup before its first iteration.  S0, S1: the
+// workgroup's slab in HBM, n x n each; w_m (m), o_n, e_n (n) and scr (SB_BLOCK): LDS.  On return S0 = H^-1, or false when a pivot of
+// the Cholesky factor is not positive and finite (the same value is read by every thread, so the workgroup returns as one).
+//   1. H = rho_x I + P + A' R_y^-1 A, row i as (A' (R_y^-1 (A e_i)) + P e_i) + rho_x e_i: the two products of the iteration
+//      (sb_mv), so every element's sum is taken in the order of the padded rows, fixed by the pattern alone.  No atomics.
+//   2. H = L L', right-looking: column j is scaled by one pass (kept in scr), the trailing lower triangle updated by all threads.
+//   3. X = L^-1 by forward substitution, thread c its column c (it reads only what it wrote itself); H^-1 = X' X, element (a, b)
+//      and (b, a) from the same products in the same order, so the inverse is symmetric to the bit.
+// Every loop is bounded by n, m or the row widths.
+__device__ __forceinline__ bool sb_factor(const real *__restrict__ Av, const int *__restrict__ Ai, int wA, const real *__restrict__ Atv,
+                                          const int *__restrict__ Ati, int wAt, const real *__restrict__ Pd, int n, int m, int z,
+                                          real rho_x, real rz, real rc, real *S0, real *S1, real *w_m, real *o_n, real *e_n, real *scr) {
+  const int t = threadIdx.x;
+  for (int i = 0; i < n; ++i) {
+    if (t < n) e_n[t] = t == i ? (real)1 : (real)0;
+    __syncthreads();
+    sb_mv<true>(Av, Ai, wA, m, e_n, w_m, scr);
+    for (int r = t; r < m; r += SB_BLOCK) w_m[r] = w_m[r] / (r < z ? rz : rc);
+    __syncthreads();
+    sb_mv<true>(Atv, Ati, wAt, n, w_m, o_n, scr);
+    if (t < n) {
+      real h = o_n[t];
+      if (Pd) h += Pd[(size_t)i * n + t];
+      if (t == i) h += rho_x;
+      S0[(size_t)i * n + t] = h;
+    }
+  }
+  __syncthreads();
+  for (int j = 0; j < n; ++j) {
+    const real d = S0[(size_t)j * n + j];
+    if (!(d > (real)0) || !isfinite(d)) return false;
+    const real rd = sqrt(d);
+    const int cnt = n - 1 - j;
+    if (t < cnt) {
+      const size_t e = (size_t)(j + 1 + t) * n + j;
+      const real v = S0[e] / rd;
+      scr[t] = v;
+      S0[e] = v;
+    }
+    __syncthreads(); // every thread has read the pivot
+    if (t == 0) S0[(size_t)j * n + j] = rd;
+    for (int e = t; e < cnt * cnt; e += SB_BLOCK) {
+      const int ii = e / cnt, kk = e - ii * cnt;
+      if (kk <= ii) S0[(size_t)(j + 1 + ii) * n + (j + 1 + kk)] -= scr[ii] * scr[kk];
+    }
+    __syncthreads();
+  }
+  // n of the 256 threads work here, each a chain of O(n^2) reads of what it wrote itself: the serial part of the factor.  The
+  // whole factor was measured at 0.6 - 2.8 % of a values solve at (n, m) = (128, 384) (profiles/small_values.md), so it is left simple
+  if (t < n) {
+    for (int i = 0; i < n; ++i) {
+      real x = 0;
+      if (i >= t) {
+        x = i == t ? (real)1 : (real)0;
+        for (int k = t; k < i; ++k) x -= S0[(size_t)i * n + k] * S1[(size_t)k * n + t];
+        x /= S0[(size_t)i * n + i];
+      }
+      S1[(size_t)i * n + t] = x;
+    }
+  }
+  __syncthreads();
+  for (int e = t; e < n * n; e += SB_BLOCK) {
+    const int r = e / n, c = e - r * n;
+    real h = 0;
+    for (int i = max(r, c); i < n; ++i) h += S1[(size_t)i * n + r] * S1[(size_t)i * n + c];
+    S0[e] = h;
+  }
+  __syncthreads();
+  return true;
 }
 
 __device__ __forceinline__ real sb_safediv(real x, real y) { return y < (real)DIV_EPS_TOL ? x / (real)DIV_EPS_TOL : x / y; }
@@ -115,8 +197,10 @@ __device__ int sb_has_converged(const real *q, const SbArgs &a, real sg, real nm
   return 0;
 }
 
-// two waves per SIMD, so that two workgroups share a CU at the largest size
-__global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const SbArgs a) {
+// two waves per SIMD, so that two workgroups share a CU at the largest size.  OWN = false: the matrices and H^-1 are the object's,
+// shared by all problems.  OWN = true: the problem's own values, and H^-1 from the factor the workgroup runs first (sb_factor).
+template <bool OWN>
+__global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditional_t<OWN, SbArgsOwn, SbArgs> a) {
   extern __shared__ __align__(16) unsigned char sb_lds_raw[];
   __shared__ int next_p;
   const int n = a.n, m = a.m, l = a.l, t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -124,28 +208,29 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const SbArgs a) {
   real *sm1 = cb + l, *sm2 = sm1 + m, *sn1 = sm2 + m, *sn2 = sn1 + n, *sn3 = sn2 + n, *scr = sn3 + n, *red = scr + SB_BLOCK;
   const real rz = (real)1.0 / ((real)1000. * a.scale), rc = (real)1.0 / a.scale; // k_set_diag_r
   auto R = [&](int i) -> real { return i < n ? a.rho_x : (i < n + a.z ? rz : (i < l - 1 ? rc : (real)TAU_FACTOR)); };
+  const real *Av = a.Av, *Atv = a.Atv, *Hinv = a.Hinv, *Pd = a.Pd, *D = a.D, *E = a.E; // OWN: set per problem below
   // r[0 .. n + m) <- (R + M)^-1 r, exactly (the header comment); r in LDS
   auto lin_solve = [&](real *r) {
     for (int i = t; i < m; i += SB_BLOCK) sm1[i] = r[n + i] / R(n + i);
     __syncthreads();
-    sb_mv<true>(a.Atv, a.Ati, a.wAt, n, sm1, sn1, scr);
+    sb_mv<true>(Atv, a.Ati, a.wAt, n, sm1, sn1, scr);
     if (t < n) sn1[t] += r[t];
     __syncthreads();
-    sb_mv<false>(a.Hinv, nullptr, n, n, sn1, sn2, scr); // x0
+    sb_mv<false>(Hinv, nullptr, n, n, sn1, sn2, scr); // x0
     // one step of refinement against the KKT operator: y0 = R_y^-1 (A x0 - r_y), rho = r_x - (R_x + P) x0 - A' y0, x = x0 + H^-1 rho.
     // The residual is formed from terms of the size of the data, not of |H| |x|: the error of H^-1 along an eigenvector of H of
     // eigenvalue near rho_x (entries of H^-1 near 1 / rho_x) is seen and removed
-    sb_mv<true>(a.Av, a.Ai, a.wA, m, sn2, sm1, scr);
+    sb_mv<true>(Av, a.Ai, a.wA, m, sn2, sm1, scr);
     for (int i = t; i < m; i += SB_BLOCK) sm1[i] = (sm1[i] - r[n + i]) / R(n + i);
     __syncthreads();
-    sb_mv<true>(a.Atv, a.Ati, a.wAt, n, sm1, sn3, scr);
-    if (a.has_P) sb_mv<false>(a.Pd, nullptr, n, n, sn2, sn1, scr);
+    sb_mv<true>(Atv, a.Ati, a.wAt, n, sm1, sn3, scr);
+    if (a.has_P) sb_mv<false>(Pd, nullptr, n, n, sn2, sn1, scr);
     if (t < n) sn3[t] = ((r[t] - a.rho_x * sn2[t]) - (a.has_P ? sn1[t] : (real)0)) - sn3[t];
     __syncthreads();
-    sb_mv<false>(a.Hinv, nullptr, n, n, sn3, sn1, scr);
+    sb_mv<false>(Hinv, nullptr, n, n, sn3, sn1, scr);
     if (t < n) r[t] = sn2[t] + sn1[t];
     __syncthreads();
-    sb_mv<true>(a.Av, a.Ai, a.wA, m, r, sm1, scr);
+    sb_mv<true>(Av, a.Ai, a.wA, m, r, sm1, scr);
     for (int i = t; i < m; i += SB_BLOCK) r[n + i] = (sm1[i] - r[n + i]) / R(n + i);
     __syncthreads();
   };
@@ -155,6 +240,24 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const SbArgs a) {
     __syncthreads();
     const int p = next_p;
     if (p >= a.nprob) break;
+    if constexpr (OWN) {
+      Av = a.Av + (size_t)p * m * a.wA;
+      Atv = a.Atv + (size_t)p * n * a.wAt;
+      if (a.has_P) Pd = a.Pd + (size_t)p * n * n;
+      D = a.D + (size_t)p * m;
+      E = a.E + (size_t)p * n;
+      real *slab = a.slab + (size_t)blockIdx.x * 2 * n * n;
+      Hinv = slab;
+      // the state vectors are not live yet: the factor's scratch is sm1, sn1, sn2 and scr
+      if (!sb_factor(Av, a.Ai, a.wA, Atv, a.Ati, a.wAt, a.has_P ? Pd : nullptr, n, m, a.z, a.rho_x, rz, rc, slab, slab + (size_t)n * n,
+                     sm1, sn1, sn2, scr)) {
+        if (t == 0) { // H is not positive definite: this problem alone fails
+          a.it[2 * (size_t)p] = -1;
+          a.it[2 * (size_t)p + 1] = SCS_FAILED;
+        }
+        continue;
+      }
+    }
     const real sg = a.scal[3 * (size_t)p], nm_b = a.scal[3 * (size_t)p + 1], nm_c = a.scal[3 * (size_t)p + 2];
     for (int i = t; i < l; i += SB_BLOCK) {
       real h = 0;
@@ -282,15 +385,15 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const SbArgs a) {
       if (last || it % CONVERGED_INTERVAL == 0) {
         // ---- populate_residual_struct (:535-607): the quantities of k_resid_primal / k_resid_dual
         const real *x = u, *y = u + n, *s = rsk + n;
-        sb_mv<true>(a.Av, a.Ai, a.wA, m, x, sm1, scr);     // ax
-        sb_mv<true>(a.Atv, a.Ati, a.wAt, n, y, sn1, scr);  // aty
-        if (a.has_P) sb_mv<false>(a.Pd, nullptr, n, n, x, sn2, scr); // px
+        sb_mv<true>(Av, a.Ai, a.wA, m, x, sm1, scr);     // ax
+        sb_mv<true>(Atv, a.Ati, a.wAt, n, y, sn1, scr);  // aty
+        if (a.has_P) sb_mv<false>(Pd, nullptr, n, n, x, sn2, scr); // px
         const real tau = absval(u[l - 1]);
         const real ds = sg, inv_ds = (real)1.0 / sg, inv_ps = (real)1.0 / sg;
         {
           real q_pri = 0, q_axs = 0, q_ax = 0, o_pri = 0, o_axs = 0, o_ax = 0, o_s = 0, n_s = 0, bty = 0;
           for (int i = t; i < m; i += SB_BLOCK) {
-            const real axi = sm1[i], si = s[i], bi = cb[n + i], Di = a.D[i];
+            const real axi = sm1[i], si = s[i], bi = cb[n + i], Di = D[i];
             const real axs = axi + si, pri = axs - tau * bi, f = inv_ds / Di;
             q_pri = fmax(q_pri, absval(pri)); q_axs = fmax(q_axs, absval(axs)); q_ax = fmax(q_ax, absval(axi));
             o_pri = fmax(o_pri, absval(pri * f)); o_axs = fmax(o_axs, absval(axs * f)); o_ax = fmax(o_ax, absval(axi * f));
@@ -305,7 +408,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const SbArgs a) {
           real q_d = 0, q_px = 0, q_aty = 0, o_d = 0, o_px = 0, o_aty = 0, ctx = 0, xpx = 0;
           for (int j = t; j < n; j += SB_BLOCK) {
             const real pxi = a.has_P ? sn2[j] : (real)0, ai = sn1[j], xi = x[j], ci = cb[j];
-            const real dual = pxi + ai + tau * ci, f = inv_ps / a.E[j];
+            const real dual = pxi + ai + tau * ci, f = inv_ps / E[j];
             q_d = fmax(q_d, absval(dual)); q_px = fmax(q_px, absval(pxi)); q_aty = fmax(q_aty, absval(ai));
             o_d = fmax(o_d, absval(dual * f)); o_px = fmax(o_px, absval(pxi * f)); o_aty = fmax(o_aty, absval(ai * f));
             ctx += xi * ci;
@@ -365,6 +468,15 @@ struct ScsAmdSmall {
   bool on_device = false; // small_device_init has run
   std::vector<real> h_av, h_atv, h_Hinv, h_Pd; // what it uploads, kept on the host until then
   std::vector<int> h_ai, h_ati, h_qoff, h_qlen;
+  // own values per problem (scs_amd_small_set_values).  The pattern of init and, built at the first set call, the position maps:
+  // CSC entry of A -> its slot in the padded rows of A and of A', upper-P entry -> its dense position (the mirror is the transpose)
+  HostCsc patA, patP;
+  std::vector<size_t> mapA, mapAt, mapP;
+  long long vals_nprob = 0; // 0: no values set
+  DevBuf<real> vAv, vAtv, vPd, vD, vE, slab; // one block per problem; the slab: 2 n^2 per workgroup of the largest grid seen
+  std::vector<Scaling> vscal;                // D_p, E_p on the host: normalize_b_c, the warm start and the way out
+  size_t slab_grid = 0;
+  int grid_default_own = 0; // 0: the own-values kernel has not been set up
   ~ScsAmdSmall() {
     if (stream) {
       (void)hipStreamSynchronize(stream);
@@ -513,7 +625,7 @@ static void small_device_init(ScsAmdSmall *s) {
   s->counter.alloc(1);
   HIP_CHECK(hipStreamSynchronize(st));
   s->lds_bytes = sb_lds_values(n, m) * sizeof(real);
-  const void *kp = reinterpret_cast<const void *>(k_small_batch);
+  const void *kp = reinterpret_cast<const void *>(k_small_batch<false>);
   HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes));
   int per_cu = 0, cus = 0;
   HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, SB_BLOCK, s->lds_bytes));
@@ -587,6 +699,8 @@ ScsAmdSmall *scs_amd_small_init(const ScsData *d, const ScsCone *k, const ScsSet
   HostCsc A, P;
   A.copy_from(d->A);
   if (s->has_P) P.copy_from(d->P);
+  s->patA = A; // the pattern scs_amd_small_set_values writes values on
+  if (s->has_P) s->patP = P;
   if (stgs->normalize) {
     equilibrate(s->has_P ? &P : nullptr, A, &s->k, s->scal);
   } else {
@@ -640,8 +754,9 @@ void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[4]) {
   out[3] = (long long)(s->setup_time * 1e3);
 }
 
-scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
-                            ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+// scs_amd_small_solve (own = false) and scs_amd_small_solve_values (own = true: the values, D and E of the last set call)
+static scs_int small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                           ScsSolution *sols, ScsInfo *infos, scs_int warm_start, bool own) {
   g_small_refused = false;
   if (!s || !B || !Cc || !sols || !infos) {
     small_refuse("missing ScsAmdSmall, B, Cc, ScsSolution or ScsInfo (a NULL argument)");
@@ -666,10 +781,18 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
       return SCS_FAILED;
     }
   }
+  // what depends on the object's state comes last: the checks of the arguments above need no accepted set call
+  if (own && s->vals_nprob == 0) {
+    small_refuse("no values are set (scs_amd_small_set_values comes first)");
+    return SCS_FAILED;
+  }
+  if (own && (long long)nprob != s->vals_nprob) {
+    small_refuse("nprob = %lld, but the values were set for %lld problems", (long long)nprob, s->vals_nprob);
+    return SCS_FAILED;
+  }
   InterruptListener listener;
   const double t_call = now_ms();
   const bool warm = warm_start != 0, norm = s->stgs.normalize != 0;
-  const Scaling &sc = s->scal;
   try {
     small_device_init(s);
     HIP_CHECK(hipSetDevice(s->device));
@@ -689,6 +812,7 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
       s->hS.resize((size_t)K * 3);
       if (warm) s->hV.resize((size_t)K * l);
       for (int p = 0; p < K; ++p) { // scs_update per problem (:1287-1325) and the warm start (:660-687)
+        const Scaling &sc = own ? s->vscal[(size_t)done + p] : s->scal;
         real *b = s->hB.data() + (size_t)p * m, *c = s->hC.data() + (size_t)p * n;
         std::copy(B + (size_t)(done + p) * (size_t)ldb, B + (size_t)(done + p) * (size_t)ldb + m, b);
         std::copy(Cc + (size_t)(done + p) * (size_t)ldc, Cc + (size_t)(done + p) * (size_t)ldc + n, c);
@@ -720,7 +844,7 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
       s->dS.upload(s->hS.data(), (size_t)K * 3, st);
       if (warm) s->dV.upload(s->hV.data(), (size_t)K * l, st);
       HIP_CHECK(hipMemsetAsync(s->counter.p, 0, sizeof(int), st));
-      SbArgs a;
+      SbArgsOwn a;
       a.n = n; a.m = m; a.l = l; a.z = (int)s->k.z; a.nl = (int)s->k.l; a.qsize = (int)s->k.qsize; a.has_P = s->has_P ? 1 : 0;
       a.normalize = norm ? 1 : 0; a.max_iters = (int)s->stgs.max_iters; a.wA = s->wA; a.wAt = s->wAt; a.nprob = K; a.warm = warm ? 1 : 0;
       a.rho_x = s->stgs.rho_x; a.scale = s->stgs.scale; a.alpha = s->stgs.alpha; a.eps_abs = s->stgs.eps_abs; a.eps_rel = s->stgs.eps_rel;
@@ -729,8 +853,21 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
       a.Ai = s->Ai.p; a.Ati = s->Ati.p; a.qoff = s->qoff.p; a.qlen = s->qlen.p;
       a.Bn = s->dB.p; a.Cn = s->dC.p; a.V0 = warm ? s->dV.p : nullptr; a.scal = s->dS.p;
       a.xys = s->dXYS.p; a.q = s->dQ.p; a.it = s->dIt.p; a.counter = s->counter.p;
-      const int grid = std::min(K, s->grid_user > 0 ? s->grid_user : s->grid_default);
-      hipLaunchKernelGGL(k_small_batch, dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, a);
+      const int grid = std::min(K, s->grid_user > 0 ? s->grid_user : (own ? s->grid_default_own : s->grid_default));
+      if (own) {
+        const size_t dn = (size_t)done;
+        a.Av = s->vAv.p + dn * m * s->wA; a.Atv = s->vAtv.p + dn * n * s->wAt; a.Hinv = nullptr;
+        a.Pd = s->has_P ? s->vPd.p + dn * n * n : nullptr; a.D = s->vD.p + dn * m; a.E = s->vE.p + dn * n;
+        if ((size_t)grid > s->slab_grid) { // the slab follows the grid, not the number of problems
+          s->slab_grid = 0;
+          s->slab.alloc((size_t)grid * 2 * n * n);
+          s->slab_grid = (size_t)grid;
+        }
+        a.slab = s->slab.p;
+        hipLaunchKernelGGL(k_small_batch<true>, dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, a);
+      } else {
+        hipLaunchKernelGGL(k_small_batch<false>, dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, static_cast<const SbArgs &>(a));
+      }
       HIP_CHECK(hipGetLastError());
       const size_t ow = (size_t)n + 2 * (size_t)m;
       s->hXYS.resize((size_t)K * ow);
@@ -747,6 +884,13 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
       for (int p = 0; p < K; ++p) { // finalize (:825-969) per problem
         ScsSolution *sol = &sols[done + p];
         ScsInfo *info = &infos[done + p];
+        if (own && s->hIt[2 * (size_t)p + 1] == SCS_FAILED) { // the device factor's pivot test: this problem alone
+          memset(info, 0, sizeof *info);
+          fail_out(nullptr, m, n, sol, info, SCS_FAILED, "the reduced matrix R_x + P + A' R_y^-1 A of this problem is not positive definite",
+                   "failure");
+          continue;
+        }
+        const Scaling &sc = own ? s->vscal[(size_t)done + p] : s->scal;
         const real sg = s->hS[3 * (size_t)p];
         const real *o = s->hXYS.data() + (size_t)p * ow;
         for (int j = 0; j < n; ++j) sol->x[j] = norm ? o[j] * (sc.E[j] / sg) : o[j];
@@ -775,6 +919,138 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
     fprintf(stderr, "%s\n", ex.what());
     if (s->stream) (void)hipStreamSynchronize(s->stream); // nothing of this call may still be reading or writing
     for (scs_int p = 0; p < nprob; ++p) fail_out(nullptr, m, n, &sols[p], &infos[p], SCS_FAILED, "HIP error in scs_amd_small_solve", "failure");
+    return SCS_FAILED;
+  }
+  return 0;
+}
+
+scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                            ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  return small_solve(s, nprob, B, ldb, Cc, ldc, sols, infos, warm_start, false);
+}
+
+scs_int scs_amd_small_solve_values(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                   ScsSolution *sols, ScsInfo *infos, scs_int warm_start) {
+  return small_solve(s, nprob, B, ldb, Cc, ldc, sols, infos, warm_start, true);
+}
+
+void scs_amd_small_free_values(ScsAmdSmall *s) {
+  if (!s) return;
+  if (s->on_device) (void)hipSetDevice(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  for (DevBuf<real> *b : {&s->vAv, &s->vAtv, &s->vPd, &s->vD, &s->vE, &s->slab}) b->release();
+  std::vector<Scaling>().swap(s->vscal);
+  s->slab_grid = 0;
+  s->vals_nprob = 0;
+}
+
+scs_int scs_amd_small_set_values(ScsAmdSmall *s, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+  g_small_refused = false;
+  if (!s || !AX) {
+    small_refuse("missing ScsAmdSmall or AX (a NULL argument)");
+    return SCS_FAILED;
+  }
+  if (PX && !s->has_P) {
+    small_refuse("PX given, but the object was built without a P");
+    return SCS_FAILED;
+  }
+  if (!PX && s->has_P) {
+    small_refuse("PX missing (a NULL argument): the object was built with a P");
+    return SCS_FAILED;
+  }
+  if (nprob < 1) {
+    small_refuse("nprob < 1");
+    return SCS_FAILED;
+  }
+  const int n = s->n, m = s->m;
+  const size_t nzA = (size_t)s->patA.p[n], nzP = s->has_P ? (size_t)s->patP.p[n] : 0;
+  if ((long long)ldax < (long long)nzA || (s->has_P && (long long)ldpx < (long long)nzP)) {
+    small_refuse("short leading dimension: ldax < nnz(A) = %lld or ldpx < nnz(P) = %lld", (long long)nzA, (long long)nzP);
+    return SCS_FAILED;
+  }
+  for (scs_int p = 0; p < nprob; ++p)
+    if ((nzA && !all_finite(AX + (size_t)p * (size_t)ldax, nzA)) || (nzP && !all_finite(PX + (size_t)p * (size_t)ldpx, nzP))) {
+      small_refuse("non-finite values in AX or PX (problem %lld)", (long long)p);
+      return SCS_FAILED;
+    }
+  scs_amd_small_free_values(s); // a second set call replaces the values; a failure below leaves none
+  try {
+    small_device_init(s);
+    HIP_CHECK(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    if (s->grid_default_own == 0) {
+      const void *kp = reinterpret_cast<const void *>(k_small_batch<true>);
+      HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes));
+      int per_cu = 0, cus = 0;
+      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, SB_BLOCK, s->lds_bytes));
+      HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+      s->grid_default_own = std::max(1, cus) * std::max(1, per_cu);
+    }
+    const size_t wA = s->wA, wAt = s->wAt, szA = (size_t)m * wA, szAt = (size_t)n * wAt, szP = s->has_P ? (size_t)n * n : 0;
+    if (s->mapA.size() != nzA || s->mapAt.size() != nzA) { // the slots small_ell gives the entries, in its order
+      s->mapA.resize(nzA);
+      s->mapAt.resize(nzA);
+      std::vector<int> cr(m, 0);
+      for (int j = 0; j < n; ++j)
+        for (eoff e = s->patA.p[j]; e < s->patA.p[j + 1]; ++e) {
+          const int r = s->patA.i[e];
+          s->mapA[e] = (size_t)(cr[r]++) * m + r;
+          s->mapAt[e] = (size_t)(e - s->patA.p[j]) * n + j;
+        }
+      s->mapP.resize(nzP);
+      for (int j = 0; j < n && s->has_P; ++j)
+        for (eoff e = s->patP.p[j]; e < s->patP.p[j + 1]; ++e) s->mapP[e] = (size_t)s->patP.i[e] * n + j;
+    }
+    const size_t K = (size_t)nprob;
+    s->vAv.alloc(K * szA);
+    s->vAtv.alloc(K * szAt);
+    if (s->has_P) s->vPd.alloc(K * szP);
+    s->vD.alloc(K * m);
+    s->vE.alloc(K * n);
+    s->vscal.resize(K);
+    // staged in blocks of problems of about 32 MB; the padding of the rows and the zeros of P are written once
+    const size_t per = szA + szAt + szP + m + n, blk = std::max<size_t>(1, std::min<size_t>(K, ((size_t)4 << 20) / per));
+    std::vector<real> hAv(blk * szA, (real)0), hAtv(blk * szAt, (real)0), hPd(blk * szP, (real)0), hD(blk * m), hE(blk * n);
+    HostCsc A = s->patA, P;
+    if (s->has_P) P = s->patP;
+    for (size_t p0 = 0; p0 < K; p0 += blk) {
+      const size_t kb = std::min(blk, K - p0);
+      for (size_t q = 0; q < kb; ++q) {
+        const size_t p = p0 + q;
+        Scaling &sc = s->vscal[p];
+        std::copy(AX + p * (size_t)ldax, AX + p * (size_t)ldax + nzA, A.x.begin());
+        if (s->has_P) std::copy(PX + p * (size_t)ldpx, PX + p * (size_t)ldpx + nzP, P.x.begin());
+        if (s->stgs.normalize) {
+          equilibrate(s->has_P ? &P : nullptr, A, &s->k, sc);
+        } else {
+          sc.D.assign(m, (real)1);
+          sc.E.assign(n, (real)1);
+        }
+        real *av = hAv.data() + q * szA, *atv = hAtv.data() + q * szAt, *pd = hPd.data() + q * szP;
+        for (size_t e = 0; e < nzA; ++e) {
+          av[s->mapA[e]] = A.x[e];
+          atv[s->mapAt[e]] = A.x[e];
+        }
+        for (size_t e = 0; e < nzP; ++e) {
+          const size_t ij = s->mapP[e], i = ij / n, j = ij - i * n;
+          pd[ij] = P.x[e];
+          pd[j * n + i] = P.x[e];
+        }
+        std::copy(sc.D.begin(), sc.D.end(), hD.begin() + q * m);
+        std::copy(sc.E.begin(), sc.E.end(), hE.begin() + q * n);
+      }
+      HIP_CHECK(hipMemcpyAsync(s->vAv.p + p0 * szA, hAv.data(), kb * szA * sizeof(real), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(s->vAtv.p + p0 * szAt, hAtv.data(), kb * szAt * sizeof(real), hipMemcpyHostToDevice, st));
+      if (s->has_P) HIP_CHECK(hipMemcpyAsync(s->vPd.p + p0 * szP, hPd.data(), kb * szP * sizeof(real), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(s->vD.p + p0 * m, hD.data(), kb * m * sizeof(real), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(s->vE.p + p0 * n, hE.data(), kb * n * sizeof(real), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipStreamSynchronize(st)); // the staging is written again by the next block
+    }
+    s->vals_nprob = (long long)nprob;
+  } catch (const std::exception &ex) {
+    fprintf(stderr, "%s\n", ex.what());
+    scs_amd_small_free_values(s);
+    fprintf(stderr, "scs_amd_small_set_values: HIP error or failed allocation: no values are set\n");
     return SCS_FAILED;
   }
   return 0;
