@@ -647,7 +647,10 @@ void scs_amd_set_residuals_every_iter(ScsWork *w, scs_int on);
  * scs_solve (exact against iterative solves: the iteration counts differ too).
  * scs_amd_small_init: d, k, stgs as scs_init takes them (d->b and d->c must be present and are not used).  Served: cones z, l and
  * q of any sizes (1 and 2 included), P present or absent, normalize 0 or 1, any scale, rho_x, alpha, eps_*, max_iters; sizes up
- * to scs_amd_small_limits: out[0] = the largest n, out[1] = the largest n + m + 1.  Not served, and named in the refusal: box,
+ * to scs_amd_small_limits: out[0] = the largest n (512), out[1] = the largest n + m + 1 (2304).  One of two instantiations of the
+ * kernel is chosen once, at init, for both solve entries: n <= 128 and n + m + 1 <= 1024 run the NARROW one (256 threads, two
+ * workgroups per CU), every other accepted size the WIDE one (1024 threads, one workgroup with the whole LDS of its CU); the
+ * bits of a problem within the narrow limits are those it always had.  Not served, and named in the refusal: box,
  * PSD, complex PSD, exponential and power cones; adaptive_scale, acceleration_lookback and time_limit_secs != 0;
  * log_csv_filename and write_data_filename; a size over a limit; a NULL argument; non-finite values in A or P; a problem
  * scs_init's validation rejects; a reduced matrix that is not positive definite (an indefinite P).  A refused init returns NULL;
@@ -668,9 +671,11 @@ void scs_amd_set_residuals_every_iter(ScsWork *w, scs_int on);
  * CUs x workgroups per CU by the kernel's LDS; never more than the problems of the launch); returns 0, or -1 on a bad argument.
  * scs_amd_small_get_counters, summed over the object's life: out[0] launches, out[1] workgroups launched, out[2] problems,
  * out[3] iterations (the sum of infos[p].iter).  scs_amd_small_get_occupancy: out[0] workgroups per CU, out[1] LDS bytes per
- * workgroup, out[2] the default grid, out[3] the setup time of init in microseconds.
+ * workgroup, out[2] the default grid (what the device side sets: out[0] and out[1] are 0 before the first accepted solve), out[3] the setup time of init in
+ * microseconds, out[4] the threads of a workgroup of the object's instantiation: 256 (narrow) or 1024 (wide), known from init on.
  * Memory: the padded rows of A and A', three dense n x n matrices, and per problem of the largest launch 2 (n + 2 m) + 27 values
- * (+ n + m + 1 once a call has warm-started), in HBM; 6 (n + m + 1) + 2 m + 3 n + 264 values of LDS per workgroup.
+ * (+ n + m + 1 once a call has warm-started), in HBM; 6 (n + m + 1) + 2 m + 3 n values of LDS per workgroup plus 264 (narrow) or
+ * 1040 (wide).
  * One caller thread per object; several GPUs are not used. */
 typedef struct ScsAmdSmall ScsAmdSmall;
 ScsAmdSmall *scs_amd_small_init(const ScsData *d, const ScsCone *k, const ScsSettings *stgs);
@@ -680,7 +685,7 @@ scs_int scs_amd_small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, s
                             ScsSolution *sols, ScsInfo *infos, scs_int warm_start);
 scs_int scs_amd_small_set_grid(ScsAmdSmall *s, scs_int workgroups);
 void scs_amd_small_get_counters(const ScsAmdSmall *s, long long out[4]);
-void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[4]);
+void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[5]);
 void scs_amd_small_finish(ScsAmdSmall *s);
 /* ---- the same batch with OWN VALUES of A and P per problem, on the pattern the object was built with ----
  * scs_amd_small_set_values: AX is nnz(A) x nprob and PX nnz(upper P) x nprob (given exactly when the object was built with a P),

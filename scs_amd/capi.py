@@ -326,7 +326,7 @@ def bind_api(lib, T, full=True, linsys=True, cones=True, stats=True):
             lib.scs_amd_small_get_counters.restype = None
             lib.scs_amd_small_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
             lib.scs_amd_small_get_occupancy.restype = None
-            lib.scs_amd_small_get_occupancy.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 4)]
+            lib.scs_amd_small_get_occupancy.argtypes = [C.c_void_p, C.POINTER(C.c_longlong * 5)]
             lib.scs_amd_small_finish.restype = None
             lib.scs_amd_small_finish.argtypes = [C.c_void_p]
     lib._scs_types = T

@@ -14,24 +14,27 @@
 // A and A' are read in padded-row (ELL) form, entry k of all rows adjacent, so a workgroup's lanes read consecutive addresses; the
 // matrices are shared by all workgroups and stay in L2.
 //
-// Determinism: a workgroup owns a problem; every sum is taken in an order fixed by (n, m, the pattern) alone -- per-thread partial
-// sums over a fixed index range, combined by wave shuffles and a fixed loop over the four waves.  No floating-point atomics.  The
+// Determinism: a workgroup owns a problem; every sum is taken in an order fixed by (n, m, the pattern, the block size) alone -- per-thread partial
+// sums over a fixed index range, combined by wave shuffles and a fixed loop over the workgroup's waves.  No floating-point atomics.  The
 // only atomic is the integer counter problems are taken from, so a problem's bits depend neither on the grid, on nprob, on its
 // index nor on its neighbours.  Every loop is bounded by max_iters, n, m, the row widths or the cone sizes.
 //
 // scs_amd_small_set_values / scs_amd_small_solve_values: the same batch with every problem's OWN values of A and P on the pattern
 // of init.  The host equilibrates every problem and writes its values into the problem's own padded rows and dense P; H is then
 // per problem, and the problem's workgroup assembles, factors and inverts it in working precision before the first iteration
-// (sb_factor, k_small_batch<true>).  k_small_batch<false> is the shared kernel, unchanged.
+// (sb_factor, k_small_batch<true, .>).  k_small_batch<false, .> is the shared kernel, unchanged.
 #include <cstdarg>
 #include <memory>
 #include <type_traits>
 
 namespace scsamd {
 
-constexpr int SB_BLOCK = 256;   // 4 waves, one per SIMD: see DESIGN.md 8e for the choice against one wave per problem
-constexpr int SB_MAX_N = 128;   // H, H^-1 and P are dense n x n
-constexpr int SB_MAX_L = 1024;  // n + m + 1: 6 l + 2 m + 3 n + 264 values of LDS
+// Two instantiations of one kernel.  NARROW: 4 waves, one per SIMD, two workgroups per CU; n <= SB_NARROW_N and
+// n + m + 1 <= SB_NARROW_L.  WIDE: 16 waves, four per SIMD, one workgroup with the whole LDS of its CU; every other accepted size.
+constexpr int SB_BLOCK = 256, SB_BLOCK_WIDE = 1024;
+constexpr int SB_NARROW_N = 128, SB_NARROW_L = 1024;
+constexpr int SB_MAX_N = 512;   // H, H^-1 and P are dense n x n; one thread per entry of an n-vector and two per dense output
+constexpr int SB_MAX_L = 2304;  // n + m + 1: 6 l + 2 m + 3 n + BLOCK + 16 values of LDS, 159 856 B of the CU's 160 KiB at (512, 1791)
 constexpr int SB_QS = NQ;       // stride of a problem's reduced scalars (Q_* above)
 constexpr int SB_CHUNK = 32768; // problems per launch: SIGINT is looked at between launches
 constexpr int SB_SERIAL_Q = 16; // second-order cones up to this size are projected by one thread, larger ones by one wave
@@ -52,16 +55,19 @@ struct SbArgsOwn : SbArgs {
   real *slab;
 };
 
-static size_t sb_lds_values(int n, int m) { return 6 * (size_t)(n + m + 1) + 2 * (size_t)m + 3 * (size_t)n + SB_BLOCK + 8; }
+// scr (block values) and red (a slot per wave, 8 at the least)
+static size_t sb_lds_values(int n, int m, int block) {
+  return 6 * (size_t)(n + m + 1) + 2 * (size_t)m + 3 * (size_t)n + block + std::max(8, block / 64);
+}
 
-// out[j] = sum_{k < W} val[k * cols + j] * x[SPARSE ? idx[k * cols + j] : k],  j < cols; x, out and scr (SB_BLOCK values) in LDS.
-// cols <= SB_BLOCK / 2: SB_BLOCK / cols threads share an output, each a fixed range of k, combined in index order.  Barrier on exit.
-template <bool SPARSE>
+// out[j] = sum_{k < W} val[k * cols + j] * x[SPARSE ? idx[k * cols + j] : k],  j < cols; x, out and scr (BLOCK values) in LDS.
+// cols <= BLOCK / 2: BLOCK / cols threads share an output, each a fixed range of k, combined in index order.  Barrier on exit.
+template <bool SPARSE, int BLOCK>
 __device__ __forceinline__ void sb_mv(const real *__restrict__ val, const int *__restrict__ idx, int W, int cols, const real *x,
                                       real *out, real *scr) {
   const int t = threadIdx.x;
-  if (cols > SB_BLOCK / 2) {
-    for (int j = t; j < cols; j += SB_BLOCK) {
+  if (cols > BLOCK / 2) {
+    for (int j = t; j < cols; j += BLOCK) {
       real s = 0;
 #pragma unroll 4
       for (int k = 0; k < W; ++k) s += val[(size_t)k * cols + j] * x[SPARSE ? idx[(size_t)k * cols + j] : k];
@@ -69,7 +75,7 @@ __device__ __forceinline__ void sb_mv(const real *__restrict__ val, const int *_
     }
     __syncthreads();
   } else {
-    const int nc = SB_BLOCK / cols, c = t / cols, j = t - c * cols, per = (W + nc - 1) / nc;
+    const int nc = BLOCK / cols, c = t / cols, j = t - c * cols, per = (W + nc - 1) / nc;
     if (c < nc) {
       const int k0 = c * per, k1 = min(W, k0 + per);
       real s = 0;
@@ -88,7 +94,7 @@ __device__ __forceinline__ void sb_mv(const real *__restrict__ val, const int *_
 }
 
 // The per-problem factor of the own-values kernel, run by the problem's workgroup before its first iteration.  S0, S1: the
-// workgroup's slab in HBM, n x n each; w_m (m), o_n, e_n (n) and scr (SB_BLOCK): LDS.  On return S0 = H^-1, or false when a pivot of
+// workgroup's slab in HBM, n x n each; w_m (m), o_n, e_n (n) and scr (BLOCK): LDS.  On return S0 = H^-1, or false when a pivot of
 // the Cholesky factor is not positive and finite (the same value is read by every thread, so the workgroup returns as one).
 //   1. H = rho_x I + P + A' R_y^-1 A, row i as (A' (R_y^-1 (A e_i)) + P e_i) + rho_x e_i: the two products of the iteration
 //      (sb_mv), so every element's sum is taken in the order of the padded rows, fixed by the pattern alone.  No atomics.
@@ -96,6 +102,7 @@ __device__ __forceinline__ void sb_mv(const real *__restrict__ val, const int *_
 //   3. X = L^-1 by forward substitution, thread c its column c (it reads only what it wrote itself); H^-1 = X' X, element (a, b)
 //      and (b, a) from the same products in the same order, so the inverse is symmetric to the bit.
 // Every loop is bounded by n, m or the row widths.
+template <int BLOCK>
 __device__ __forceinline__ bool sb_factor(const real *__restrict__ Av, const int *__restrict__ Ai, int wA, const real *__restrict__ Atv,
                                           const int *__restrict__ Ati, int wAt, const real *__restrict__ Pd, int n, int m, int z,
                                           real rho_x, real rz, real rc, real *S0, real *S1, real *w_m, real *o_n, real *e_n, real *scr) {
@@ -103,10 +110,10 @@ __device__ __forceinline__ bool sb_factor(const real *__restrict__ Av, const int
   for (int i = 0; i < n; ++i) {
     if (t < n) e_n[t] = t == i ? (real)1 : (real)0;
     __syncthreads();
-    sb_mv<true>(Av, Ai, wA, m, e_n, w_m, scr);
-    for (int r = t; r < m; r += SB_BLOCK) w_m[r] = w_m[r] / (r < z ? rz : rc);
+    sb_mv<true, BLOCK>(Av, Ai, wA, m, e_n, w_m, scr);
+    for (int r = t; r < m; r += BLOCK) w_m[r] = w_m[r] / (r < z ? rz : rc);
     __syncthreads();
-    sb_mv<true>(Atv, Ati, wAt, n, w_m, o_n, scr);
+    sb_mv<true, BLOCK>(Atv, Ati, wAt, n, w_m, o_n, scr);
     if (t < n) {
       real h = o_n[t];
       if (Pd) h += Pd[(size_t)i * n + t];
@@ -128,13 +135,13 @@ __device__ __forceinline__ bool sb_factor(const real *__restrict__ Av, const int
     }
     __syncthreads(); // every thread has read the pivot
     if (t == 0) S0[(size_t)j * n + j] = rd;
-    for (int e = t; e < cnt * cnt; e += SB_BLOCK) {
+    for (int e = t; e < cnt * cnt; e += BLOCK) {
       const int ii = e / cnt, kk = e - ii * cnt;
       if (kk <= ii) S0[(size_t)(j + 1 + ii) * n + (j + 1 + kk)] -= scr[ii] * scr[kk];
     }
     __syncthreads();
   }
-  // n of the 256 threads work here, each a chain of O(n^2) reads of what it wrote itself: the serial part of the factor.  The
+  // n of the workgroup's threads work here, each a chain of O(n^2) reads of what it wrote itself: the serial part of the factor.  The
   // whole factor was measured at 0.6 - 2.8 % of a values solve at (n, m) = (128, 384) (profiles/small_values.md), so it is left simple
   if (t < n) {
     for (int i = 0; i < n; ++i) {
@@ -148,7 +155,7 @@ __device__ __forceinline__ bool sb_factor(const real *__restrict__ Av, const int
     }
   }
   __syncthreads();
-  for (int e = t; e < n * n; e += SB_BLOCK) {
+  for (int e = t; e < n * n; e += BLOCK) {
     const int r = e / n, c = e - r * n;
     real h = 0;
     for (int i = max(r, c); i < n; ++i) h += S1[(size_t)i * n + r] * S1[(size_t)i * n + c];
@@ -197,41 +204,42 @@ __device__ int sb_has_converged(const real *q, const SbArgs &a, real sg, real nm
   return 0;
 }
 
-// two waves per SIMD, so that two workgroups share a CU at the largest size.  OWN = false: the matrices and H^-1 are the object's,
-// shared by all problems.  OWN = true: the problem's own values, and H^-1 from the factor the workgroup runs first (sb_factor).
-template <bool OWN>
-__global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditional_t<OWN, SbArgsOwn, SbArgs> a) {
+// BLOCK = 256: two waves per SIMD, so that two workgroups share a CU at the narrow limits.  BLOCK = 1024: four waves per SIMD, one
+// workgroup per CU.  OWN = false: the matrices and H^-1 are the object's, shared by all problems.  OWN = true: the problem's own
+// values, and H^-1 from the factor the workgroup runs first (sb_factor).
+template <bool OWN, int BLOCK>
+__global__ __launch_bounds__(BLOCK, BLOCK == SB_BLOCK ? 2 : 1) void k_small_batch(const std::conditional_t<OWN, SbArgsOwn, SbArgs> a) {
   extern __shared__ __align__(16) unsigned char sb_lds_raw[];
   __shared__ int next_p;
   const int n = a.n, m = a.m, l = a.l, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   real *u = reinterpret_cast<real *>(sb_lds_raw), *u_t = u + l, *v = u_t + l, *rsk = v + l, *g = rsk + l, *cb = g + l; // cb = [c; b]
-  real *sm1 = cb + l, *sm2 = sm1 + m, *sn1 = sm2 + m, *sn2 = sn1 + n, *sn3 = sn2 + n, *scr = sn3 + n, *red = scr + SB_BLOCK;
+  real *sm1 = cb + l, *sm2 = sm1 + m, *sn1 = sm2 + m, *sn2 = sn1 + n, *sn3 = sn2 + n, *scr = sn3 + n, *red = scr + BLOCK;
   const real rz = (real)1.0 / ((real)1000. * a.scale), rc = (real)1.0 / a.scale; // k_set_diag_r
   auto R = [&](int i) -> real { return i < n ? a.rho_x : (i < n + a.z ? rz : (i < l - 1 ? rc : (real)TAU_FACTOR)); };
   const real *Av = a.Av, *Atv = a.Atv, *Hinv = a.Hinv, *Pd = a.Pd, *D = a.D, *E = a.E; // OWN: set per problem below
   // r[0 .. n + m) <- (R + M)^-1 r, exactly (the header comment); r in LDS
   auto lin_solve = [&](real *r) {
-    for (int i = t; i < m; i += SB_BLOCK) sm1[i] = r[n + i] / R(n + i);
+    for (int i = t; i < m; i += BLOCK) sm1[i] = r[n + i] / R(n + i);
     __syncthreads();
-    sb_mv<true>(Atv, a.Ati, a.wAt, n, sm1, sn1, scr);
+    sb_mv<true, BLOCK>(Atv, a.Ati, a.wAt, n, sm1, sn1, scr);
     if (t < n) sn1[t] += r[t];
     __syncthreads();
-    sb_mv<false>(Hinv, nullptr, n, n, sn1, sn2, scr); // x0
+    sb_mv<false, BLOCK>(Hinv, nullptr, n, n, sn1, sn2, scr); // x0
     // one step of refinement against the KKT operator: y0 = R_y^-1 (A x0 - r_y), rho = r_x - (R_x + P) x0 - A' y0, x = x0 + H^-1 rho.
     // The residual is formed from terms of the size of the data, not of |H| |x|: the error of H^-1 along an eigenvector of H of
     // eigenvalue near rho_x (entries of H^-1 near 1 / rho_x) is seen and removed
-    sb_mv<true>(Av, a.Ai, a.wA, m, sn2, sm1, scr);
-    for (int i = t; i < m; i += SB_BLOCK) sm1[i] = (sm1[i] - r[n + i]) / R(n + i);
+    sb_mv<true, BLOCK>(Av, a.Ai, a.wA, m, sn2, sm1, scr);
+    for (int i = t; i < m; i += BLOCK) sm1[i] = (sm1[i] - r[n + i]) / R(n + i);
     __syncthreads();
-    sb_mv<true>(Atv, a.Ati, a.wAt, n, sm1, sn3, scr);
-    if (a.has_P) sb_mv<false>(Pd, nullptr, n, n, sn2, sn1, scr);
+    sb_mv<true, BLOCK>(Atv, a.Ati, a.wAt, n, sm1, sn3, scr);
+    if (a.has_P) sb_mv<false, BLOCK>(Pd, nullptr, n, n, sn2, sn1, scr);
     if (t < n) sn3[t] = ((r[t] - a.rho_x * sn2[t]) - (a.has_P ? sn1[t] : (real)0)) - sn3[t];
     __syncthreads();
-    sb_mv<false>(Hinv, nullptr, n, n, sn3, sn1, scr);
+    sb_mv<false, BLOCK>(Hinv, nullptr, n, n, sn3, sn1, scr);
     if (t < n) r[t] = sn2[t] + sn1[t];
     __syncthreads();
-    sb_mv<true>(Av, a.Ai, a.wA, m, r, sm1, scr);
-    for (int i = t; i < m; i += SB_BLOCK) r[n + i] = (sm1[i] - r[n + i]) / R(n + i);
+    sb_mv<true, BLOCK>(Av, a.Ai, a.wA, m, r, sm1, scr);
+    for (int i = t; i < m; i += BLOCK) r[n + i] = (sm1[i] - r[n + i]) / R(n + i);
     __syncthreads();
   };
   for (int taken = 0; taken < a.nprob; ++taken) { // a workgroup takes at most nprob problems
@@ -249,7 +257,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
       real *slab = a.slab + (size_t)blockIdx.x * 2 * n * n;
       Hinv = slab;
       // the state vectors are not live yet: the factor's scratch is sm1, sn1, sn2 and scr
-      if (!sb_factor(Av, a.Ai, a.wA, Atv, a.Ati, a.wAt, a.has_P ? Pd : nullptr, n, m, a.z, a.rho_x, rz, rc, slab, slab + (size_t)n * n,
+      if (!sb_factor<BLOCK>(Av, a.Ai, a.wA, Atv, a.Ati, a.wAt, a.has_P ? Pd : nullptr, n, m, a.z, a.rho_x, rz, rc, slab, slab + (size_t)n * n,
                      sm1, sn1, sn2, scr)) {
         if (t == 0) { // H is not positive definite: this problem alone fails
           a.it[2 * (size_t)p] = -1;
@@ -259,7 +267,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
       }
     }
     const real sg = a.scal[3 * (size_t)p], nm_b = a.scal[3 * (size_t)p + 1], nm_c = a.scal[3 * (size_t)p + 2];
-    for (int i = t; i < l; i += SB_BLOCK) {
+    for (int i = t; i < l; i += BLOCK) {
       real h = 0;
       if (i < n) h = a.Cn[(size_t)p * n + i];
       else if (i < l - 1) h = a.Bn[(size_t)p * m + (i - n)];
@@ -280,21 +288,21 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
         // ---- normalize_v, u_t = [R_x v; -R_y v; v_tau]
         if (it >= FEASIBLE_ITERS) {
           real s = 0;
-          for (int i = t; i < l; i += SB_BLOCK) s += v[i] * v[i];
+          for (int i = t; i < l; i += BLOCK) s += v[i] * v[i];
           const real nrm = sqrt(block_sum(s, red));
           if (nrm != (real)0) {
             const real f = sqrt((real)l) * (real)1. / nrm;
-            for (int i = t; i < l; i += SB_BLOCK) v[i] *= f;
+            for (int i = t; i < l; i += BLOCK) v[i] *= f;
           }
         }
-        for (int i = t; i < l; i += SB_BLOCK) u_t[i] = i < n ? v[i] * R(i) : (i < l - 1 ? -v[i] * R(i) : v[i]);
+        for (int i = t; i < l; i += BLOCK) u_t[i] = i < n ? v[i] * R(i) : (i < l - 1 ? -v[i] * R(i) : v[i]);
         __syncthreads();
         lin_solve(u_t);
         // ---- root_plus
         real tau_t = 1;
         if (it >= FEASIBLE_ITERS) {
           real gg = 0, mug = 0, pg = 0, pp = 0, pmu = 0;
-          for (int i = t; i < l - 1; i += SB_BLOCK) {
+          for (int i = t; i < l - 1; i += BLOCK) {
             const real ri = R(i), gi = g[i], pi = u_t[i], mui = v[i];
             gg += gi * gi * ri;
             mug += mui * gi * ri;
@@ -312,7 +320,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
         }
         // ---- u_t -= tau~ g, u = 2 u_t - v, Moreau pre-scaling (sm2 = -R_y u_y)
         __syncthreads();
-        for (int i = t; i < l; i += SB_BLOCK) {
+        for (int i = t; i < l; i += BLOCK) {
           if (i < l - 1) {
             const real ut = u_t[i] + g[i] * (-tau_t);
             u_t[i] = ut;
@@ -327,7 +335,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
         }
         __syncthreads();
         // ---- second-order cones (proj_soc, src/cones.c:1250-1279)
-        for (int ci = t; ci < a.qsize; ci += SB_BLOCK) {
+        for (int ci = t; ci < a.qsize; ci += BLOCK) {
           const int len = a.qlen[ci];
           if (len > SB_SERIAL_Q || len <= 0) continue;
           real *x = sm2 + a.qoff[ci];
@@ -352,7 +360,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
             for (int k = 1; k < len; ++k) x[k] *= f;
           }
         }
-        for (int ci = wave; ci < a.qsize; ci += SB_BLOCK / 64) {
+        for (int ci = wave; ci < a.qsize; ci += BLOCK / 64) {
           const int len = a.qlen[ci];
           if (len <= SB_SERIAL_Q) continue;
           real *x = sm2 + a.qoff[ci];
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
         }
         __syncthreads();
         // ---- Moreau post, rsk = R (v + u - 2 u_t)
-        for (int i = t; i < l; i += SB_BLOCK) {
+        for (int i = t; i < l; i += BLOCK) {
           real ui = u[i];
           const real ri = R(i);
           if (i >= n && i < l - 1) {
@@ -385,14 +393,14 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
       if (last || it % CONVERGED_INTERVAL == 0) {
         // ---- populate_residual_struct (:535-607): the quantities of k_resid_primal / k_resid_dual
         const real *x = u, *y = u + n, *s = rsk + n;
-        sb_mv<true>(Av, a.Ai, a.wA, m, x, sm1, scr);     // ax
-        sb_mv<true>(Atv, a.Ati, a.wAt, n, y, sn1, scr);  // aty
-        if (a.has_P) sb_mv<false>(Pd, nullptr, n, n, x, sn2, scr); // px
+        sb_mv<true, BLOCK>(Av, a.Ai, a.wA, m, x, sm1, scr);     // ax
+        sb_mv<true, BLOCK>(Atv, a.Ati, a.wAt, n, y, sn1, scr);  // aty
+        if (a.has_P) sb_mv<false, BLOCK>(Pd, nullptr, n, n, x, sn2, scr); // px
         const real tau = absval(u[l - 1]);
         const real ds = sg, inv_ds = (real)1.0 / sg, inv_ps = (real)1.0 / sg;
         {
           real q_pri = 0, q_axs = 0, q_ax = 0, o_pri = 0, o_axs = 0, o_ax = 0, o_s = 0, n_s = 0, bty = 0;
-          for (int i = t; i < m; i += SB_BLOCK) {
+          for (int i = t; i < m; i += BLOCK) {
             const real axi = sm1[i], si = s[i], bi = cb[n + i], Di = D[i];
             const real axs = axi + si, pri = axs - tau * bi, f = inv_ds / Di;
             q_pri = fmax(q_pri, absval(pri)); q_axs = fmax(q_axs, absval(axs)); q_ax = fmax(q_ax, absval(axi));
@@ -406,7 +414,7 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
         }
         {
           real q_d = 0, q_px = 0, q_aty = 0, o_d = 0, o_px = 0, o_aty = 0, ctx = 0, xpx = 0;
-          for (int j = t; j < n; j += SB_BLOCK) {
+          for (int j = t; j < n; j += BLOCK) {
             const real pxi = a.has_P ? sn2[j] : (real)0, ai = sn1[j], xi = x[j], ci = cb[j];
             const real dual = pxi + ai + tau * ci, f = inv_ps / E[j];
             q_d = fmax(q_d, absval(dual)); q_px = fmax(q_px, absval(pxi)); q_aty = fmax(q_aty, absval(ai));
@@ -426,13 +434,13 @@ __global__ __launch_bounds__(SB_BLOCK, 2) void k_small_batch(const std::conditio
         if (status != 0) break; // like the reference, the converged iteration is not counted
       }
       // ---- dual update
-      for (int i = t; i < l; i += SB_BLOCK) v[i] += a.alpha * (u[i] - u_t[i]);
+      for (int i = t; i < l; i += BLOCK) v[i] += a.alpha * (u[i] - u_t[i]);
       __syncthreads();
     }
     // ---- the problem's result: normalised x, y, s and the reduced scalars
     real *o = a.xys + (size_t)p * (n + 2 * (size_t)m);
-    for (int i = t; i < n + m; i += SB_BLOCK) o[i] = u[i];
-    for (int i = t; i < m; i += SB_BLOCK) o[n + m + i] = rsk[n + i];
+    for (int i = t; i < n + m; i += BLOCK) o[i] = u[i];
+    for (int i = t; i < m; i += BLOCK) o[n + m + i] = rsk[n + i];
     if (t == 0) {
 #pragma unroll
       for (int k = 0; k < Q_COUNT; ++k) a.q[(size_t)p * SB_QS + k] = q[k];
@@ -462,6 +470,7 @@ struct ScsAmdSmall {
   std::vector<real> hB, hC, hV, hS, hXYS, hQ;
   std::vector<int> hIt;
   int grid_user = 0, grid_default = 1, wg_per_cu = 0;
+  int block = SB_BLOCK; // the instantiation, chosen once at init: SB_BLOCK (narrow) or SB_BLOCK_WIDE
   size_t lds_bytes = 0;
   long long counters[4] = {0, 0, 0, 0};
   double setup_time = 0;
@@ -575,6 +584,27 @@ static int small_ell(const HostCsc &A, bool by_row, std::vector<real> &val, std:
   return W;
 }
 
+// the instantiation an object runs: k_small_batch<own, s->block>
+static const void *small_kernel(const ScsAmdSmall *s, bool own) {
+  if (s->block == SB_BLOCK)
+    return own ? reinterpret_cast<const void *>(k_small_batch<true, SB_BLOCK>) : reinterpret_cast<const void *>(k_small_batch<false, SB_BLOCK>);
+  return own ? reinterpret_cast<const void *>(k_small_batch<true, SB_BLOCK_WIDE>)
+             : reinterpret_cast<const void *>(k_small_batch<false, SB_BLOCK_WIDE>);
+}
+
+// the dynamic LDS of the instantiation and what the CU then holds of it; 0 workgroups is an error, not a grid of one (the wide
+// kernel asks for nearly the whole CU: a build whose static LDS leaves less room must say so).  Throws HipError.
+static int small_wg_per_cu(const ScsAmdSmall *s, bool own) {
+  const void *kp = small_kernel(s, own);
+  HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes));
+  int per_cu = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, s->block, s->lds_bytes));
+  if (per_cu < 1)
+    throw HipError("scs_amd_small: no workgroup of " + std::to_string(s->block) + " threads with " + std::to_string(s->lds_bytes) +
+                   " B of LDS fits a CU of this device");
+  return per_cu;
+}
+
 static void small_ensure(ScsAmdSmall *s, size_t chunk, bool warm) {
   if (chunk > s->cap) {
     const size_t n = s->n, m = s->m;
@@ -624,13 +654,10 @@ static void small_device_init(ScsAmdSmall *s) {
   upi(s->qlen, s->h_qlen);
   s->counter.alloc(1);
   HIP_CHECK(hipStreamSynchronize(st));
-  s->lds_bytes = sb_lds_values(n, m) * sizeof(real);
-  const void *kp = reinterpret_cast<const void *>(k_small_batch<false>);
-  HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes));
-  int per_cu = 0, cus = 0;
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, SB_BLOCK, s->lds_bytes));
+  s->lds_bytes = sb_lds_values(n, m, s->block) * sizeof(real);
+  int cus = 0;
+  s->wg_per_cu = small_wg_per_cu(s, false);
   HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-  s->wg_per_cu = std::max(1, per_cu);
   s->grid_default = std::max(1, cus) * s->wg_per_cu; // what the chip holds at once
   s->on_device = true;
   for (std::vector<real> *v : {&s->h_av, &s->h_atv, &s->h_Hinv, &s->h_Pd}) std::vector<real>().swap(*v);
@@ -689,6 +716,7 @@ ScsAmdSmall *scs_amd_small_init(const ScsData *d, const ScsCone *k, const ScsSet
   std::unique_ptr<ScsAmdSmall> s(new ScsAmdSmall());
   const int n = s->n = (int)d->n, m = s->m = (int)d->m;
   s->l = n + m + 1;
+  s->block = n <= SB_NARROW_N && s->l <= SB_NARROW_L ? SB_BLOCK : SB_BLOCK_WIDE; // both entries, for the object's life
   s->stgs = *stgs;
   s->stgs.write_data_filename = s->stgs.log_csv_filename = nullptr;
   s->k = *k;
@@ -745,13 +773,16 @@ void scs_amd_small_get_counters(const ScsAmdSmall *s, long long out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = s->counters[i];
 }
 
-// out[0] workgroups per CU the kernel's LDS allows, out[1] LDS bytes per workgroup, out[2] the default grid, out[3] setup time in microseconds
-void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[4]) {
+// out[0] workgroups per CU the kernel's LDS allows, out[1] LDS bytes per workgroup, out[2] the default grid, out[3] setup time in
+// microseconds (0 and 1 are 0 before the first solve); out[4] the threads of a workgroup of the object's instantiation, 256 (narrow)
+// or 1024 (wide), known from init on
+void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[5]) {
   if (!s || !out) return;
   out[0] = s->wg_per_cu;
   out[1] = (long long)s->lds_bytes;
   out[2] = s->grid_default;
   out[3] = (long long)(s->setup_time * 1e3);
+  out[4] = s->block;
 }
 
 // scs_amd_small_solve (own = false) and scs_amd_small_solve_values (own = true: the values, D and E of the last set call)
@@ -864,9 +895,12 @@ static scs_int small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, sc
           s->slab_grid = (size_t)grid;
         }
         a.slab = s->slab.p;
-        hipLaunchKernelGGL(k_small_batch<true>, dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, a);
+        if (s->block == SB_BLOCK) hipLaunchKernelGGL((k_small_batch<true, SB_BLOCK>), dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, a);
+        else hipLaunchKernelGGL((k_small_batch<true, SB_BLOCK_WIDE>), dim3(grid), dim3(SB_BLOCK_WIDE), s->lds_bytes, st, a);
       } else {
-        hipLaunchKernelGGL(k_small_batch<false>, dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, static_cast<const SbArgs &>(a));
+        const SbArgs &as = a;
+        if (s->block == SB_BLOCK) hipLaunchKernelGGL((k_small_batch<false, SB_BLOCK>), dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, as);
+        else hipLaunchKernelGGL((k_small_batch<false, SB_BLOCK_WIDE>), dim3(grid), dim3(SB_BLOCK_WIDE), s->lds_bytes, st, as);
       }
       HIP_CHECK(hipGetLastError());
       const size_t ow = (size_t)n + 2 * (size_t)m;
@@ -979,12 +1013,10 @@ scs_int scs_amd_small_set_values(ScsAmdSmall *s, scs_int nprob, const scs_float 
     HIP_CHECK(hipSetDevice(s->device));
     hipStream_t st = s->stream;
     if (s->grid_default_own == 0) {
-      const void *kp = reinterpret_cast<const void *>(k_small_batch<true>);
-      HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes));
-      int per_cu = 0, cus = 0;
-      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, SB_BLOCK, s->lds_bytes));
+      int cus = 0;
+      const int per_cu = small_wg_per_cu(s, true);
       HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-      s->grid_default_own = std::max(1, cus) * std::max(1, per_cu);
+      s->grid_default_own = std::max(1, cus) * per_cu;
     }
     const size_t wA = s->wA, wAt = s->wAt, szA = (size_t)m * wA, szAt = (size_t)n * wAt, szP = s->has_P ? (size_t)n * n : 0;
     if (s->mapA.size() != nzA || s->mapAt.size() != nzA) { // the slots small_ell gives the entries, in its order

@@ -193,11 +193,13 @@ class SmallBatch:
         return dict(zip(("launches", "workgroups", "problems", "iterations"), (int(v) for v in out)))
 
     def occupancy(self):
-        """workgroups per CU, LDS bytes per workgroup, the default grid, and the setup time in seconds"""
-        out = (ct.c_longlong * 4)()
+        """workgroups per CU, LDS bytes per workgroup (both 0 before the first solve) and the default grid, the setup time in seconds,
+        and the instantiation chosen at init: block_threads 256 / 1024, kernel 'narrow' / 'wide'"""
+        out = (ct.c_longlong * 5)()
         if self._h:
             self._lib.scs_amd_small_get_occupancy(self._h, ct.byref(out))
-        return dict(wg_per_cu=int(out[0]), lds_bytes=int(out[1]), default_grid=int(out[2]), setup_s=int(out[3]) / 1e6)
+        return dict(wg_per_cu=int(out[0]), lds_bytes=int(out[1]), default_grid=int(out[2]), setup_s=int(out[3]) / 1e6,
+                    block_threads=int(out[4]), kernel={256: "narrow", 1024: "wide"}.get(int(out[4])))
 
     def close(self):
         if self._h:
