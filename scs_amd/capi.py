@@ -485,6 +485,25 @@ def cone_rows(cone):
                3 * (cone.get("ep", 0) + cone.get("ed", 0) + len(cone.get("p", []))))
 
 
+def cone_and_settings(cone, settings, **defaults):
+    """The cone dict and the settings keywords of scs-python as `Problem` and `default_settings` take them: the legacy 'f' joins 'z',
+    a scalar for a single cone becomes a list, `use_indirect` / `gpu` / `mkl` / `linear_solver` are dropped (there is one backend),
+    file names become bytes, verbose defaults to 0 and every key of `defaults` to its value."""
+    cone = dict(cone)
+    if "f" in cone:  # scs < 3 name of the zero cone
+        cone["z"] = cone.pop("f") + cone.get("z", 0)
+    for k in ("q", "s", "cs", "p", "bu", "bl"):  # scs-python accepts scalars for single cones
+        if k in cone and np.isscalar(cone[k]):
+            cone[k] = [cone[k]]
+    kw = {k: v for k, v in settings.items() if k not in ("use_indirect", "gpu", "mkl", "linear_solver")}
+    for k in ("write_data_filename", "log_csv_filename"):
+        if isinstance(kw.get(k), str):
+            kw[k] = kw[k].encode()
+    for k, v in dict(verbose=0, **defaults).items():
+        kw.setdefault(k, v)
+    return cone, kw
+
+
 def default_settings(lib, **over):
     T = lib._scs_types
     st = T.ScsSettings()
@@ -507,6 +526,25 @@ def info_dict(info):
     d["status"] = info.status.decode()
     d["lin_sys_solver"] = info.lin_sys_solver.decode()
     return d
+
+
+class SolutionBlock:
+    """What K problems of one call come back in: X (n x K), Y and S (m x K), column-major and zero or, with warm = (X, Y, S), filled
+    from it; `sols`, an ScsSolution array over their columns, and `infos`, an ScsInfo array, to hand to the library."""
+
+    def __init__(self, T, n, m, K, warm=None):
+        self.K = K
+        self.X, self.Y, self.S = (np.zeros((rows, K), dtype=T.np_float, order="F") for rows in (n, m, m))
+        if warm is not None:
+            self.X[:], self.Y[:], self.S[:] = warm
+        self.sols, self.infos = (T.ScsSolution * max(K, 1))(), (T.ScsInfo * max(K, 1))()
+        x0, y0, s0, sz = self.X.ctypes.data, self.Y.ctypes.data, self.S.ctypes.data, np.dtype(T.np_float).itemsize
+        for k, sol in zip(range(K), self.sols):
+            sol.x, sol.y, sol.s = C.cast(x0 + k * n * sz, T.fp), C.cast(y0 + k * m * sz, T.fp), C.cast(s0 + k * m * sz, T.fp)
+
+    def results(self):
+        """K dicts in the shape of `solve`"""
+        return [dict(x=self.X[:, k].copy(), y=self.Y[:, k].copy(), s=self.S[:, k].copy(), info=info_dict(self.infos[k])) for k in range(self.K)]
 
 
 def solve(lib, prob, settings=None, warm=None, want_stats=False, profiling=False, cg_tol_override=None, **over):
@@ -625,17 +663,9 @@ def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales, stream_width=
         raise ValueError("B must be m x K and C n x K")
     m, K = B.shape
     n = Cc.shape[0]
-    X, Y, S = (np.zeros((n, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"))
-    if warm is not None:
-        X[:], Y[:], S[:] = warm
-    sols = (T.ScsSolution * max(K, 1))()
-    infos = (T.ScsInfo * max(K, 1))()
-    sz = np.dtype(f).itemsize
-    for k in range(K):
-        sols[k].x = C.cast(X.ctypes.data + k * n * sz, T.fp)
-        sols[k].y = C.cast(Y.ctypes.data + k * m * sz, T.fp)
-        sols[k].s = C.cast(S.ctypes.data + k * m * sz, T.fp)
-    ws = (1 if warm is not None else 0) if warm_start is None else int(warm_start)
+    blk = SolutionBlock(T, n, m, K, warm)
+    sols, infos = blk.sols, blk.infos
+    ws =(1 if warm is not None else 0) if warm_start is None else int(warm_start)
     sp = None
     if (scaled or stream_width is not None) and scales is not None:
         scales = np.ascontiguousarray(scales, dtype=f)
@@ -651,4 +681,4 @@ def _solve_family(lib, w, B, Cc, warm, warm_start, scaled, scales, stream_width=
         rc = lib.scs_amd_solve_family_scaled(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sp, sols, infos, ws)
     else:
         rc = lib.scs_amd_solve_family(w, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos, ws)
-    return rc, [dict(x=X[:, k].copy(), y=Y[:, k].copy(), s=S[:, k].copy(), info=info_dict(infos[k])) for k in range(K)]
+    return rc, blk.results()

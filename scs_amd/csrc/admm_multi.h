@@ -646,13 +646,7 @@ static bool family_stage_warm(ScsWork *w, const Scaling &sc, const ScsSolution &
     y[i] = ro.active ? sol.y[ro.row_new2old[i]] : sol.y[i];
     s[i] = ro.active ? sol.s[ro.row_new2old[i]] : sol.s[i];
   }
-  if (w->stgs.normalize) { // normalize_sol (src/normalize.c:64-76) with the problem's scales
-    for (int j = 0; j < n; ++j) x[j] /= (sc.E[j] / col.ds);
-    for (int i = 0; i < m; ++i) {
-      y[i] /= (sc.D[i] / col.ps);
-      s[i] *= (sc.D[i] * col.ds);
-    }
-  }
+  if (w->stgs.normalize) normalize_sol_scaled(sc, col.ps, col.ds, x, y, s); // src/normalize.c:64-76 with the problem's scales
   for (int j = 0; j < n; ++j) x[j] = x[j] != x[j] ? (real)0 : x[j];
   for (int i = 0; i < m; ++i) {
     const real t = y[i] + s[i] / ry[(size_t)i * ry_stride];
@@ -671,13 +665,7 @@ static void family_return(ScsWork *w, const Scaling &sc, const FamCol &col, bool
   if (!sol->y) sol->y = (real *)calloc(m, sizeof(real));
   if (!sol->s) sol->s = (real *)calloc(m, sizeof(real));
   real *x = f.col_x.data(), *y = f.col_y.data(), *s = f.col_s.data();
-  if (w->stgs.normalize) { // un_normalize_sol (src/normalize.c:78-91) with the problem's scales
-    for (int j = 0; j < n; ++j) x[j] *= (sc.E[j] / col.ds);
-    for (int r = 0; r < m; ++r) {
-      y[r] *= (sc.D[r] / col.ps);
-      s[r] /= (sc.D[r] * col.ds);
-    }
-  }
+  if (w->stgs.normalize) un_normalize_sol_scaled(sc, col.ps, col.ds, x, y, s); // src/normalize.c:78-91 with the problem's scales
   for (int j = 0; j < n; ++j) sol->x[ro.active ? ro.col_new2old[j] : j] = x[j];
   for (int r = 0; r < m; ++r) {
     sol->y[ro.active ? ro.row_new2old[r] : r] = y[r];

@@ -166,21 +166,23 @@ real normalize_b_c_sigma(const Scaling &sc, real *b, real *c) {
 }
 void normalize_b_c(Scaling &sc, real *b, real *c) { sc.primal_scale = sc.dual_scale = normalize_b_c_sigma(sc, b, c); }
 
-void normalize_sol(const Scaling &sc, real *x, real *y, real *s) {
-  for (size_t j = 0; j < sc.E.size(); ++j) x[j] /= (sc.E[j] / sc.dual_scale);
+void normalize_sol_scaled(const Scaling &sc, real ps, real ds, real *x, real *y, real *s) {
+  for (size_t j = 0; j < sc.E.size(); ++j) x[j] /= (sc.E[j] / ds);
   for (size_t i = 0; i < sc.D.size(); ++i) {
-    y[i] /= (sc.D[i] / sc.primal_scale);
-    s[i] *= (sc.D[i] * sc.dual_scale);
+    y[i] /= (sc.D[i] / ps);
+    s[i] *= (sc.D[i] * ds);
   }
 }
+void normalize_sol(const Scaling &sc, real *x, real *y, real *s) { normalize_sol_scaled(sc, sc.primal_scale, sc.dual_scale, x, y, s); }
 
-void un_normalize_sol(const Scaling &sc, real *x, real *y, real *s) {
-  for (size_t j = 0; j < sc.E.size(); ++j) x[j] *= (sc.E[j] / sc.dual_scale);
+void un_normalize_sol_scaled(const Scaling &sc, real ps, real ds, real *x, real *y, real *s) {
+  for (size_t j = 0; j < sc.E.size(); ++j) x[j] *= (sc.E[j] / ds);
   for (size_t i = 0; i < sc.D.size(); ++i) {
-    y[i] *= (sc.D[i] / sc.primal_scale);
-    s[i] /= (sc.D[i] * sc.dual_scale);
+    y[i] *= (sc.D[i] / ps);
+    s[i] /= (sc.D[i] * ds);
   }
 }
+void un_normalize_sol(const Scaling &sc, real *x, real *y, real *s) { un_normalize_sol_scaled(sc, sc.primal_scale, sc.dual_scale, x, y, s); }
 
 // ---- input validation (reference linsys/scs_matrix.c:65-157) -----------------
 int validate_csc(const ScsMatrix *M, int rows, int cols, bool upper_only, const char *name) {

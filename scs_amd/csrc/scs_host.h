@@ -106,6 +106,9 @@ void normalize_b_c(Scaling &sc, real *b, real *c);
 real normalize_b_c_sigma(const Scaling &sc, real *b, real *c); // the same on D, E alone: returns primal_scale = dual_scale instead of storing it
 void normalize_sol(const Scaling &sc, real *x, real *y, real *s);
 void un_normalize_sol(const Scaling &sc, real *x, real *y, real *s);
+// the same two on D, E alone, with the problem's primal_scale (ps) and dual_scale (ds) given instead of read from sc
+void normalize_sol_scaled(const Scaling &sc, real ps, real ds, real *x, real *y, real *s);
+void un_normalize_sol_scaled(const Scaling &sc, real ps, real ds, real *x, real *y, real *s);
 int validate_csc(const ScsMatrix *M, int rows, int cols, bool upper_only, const char *name);
 
 int write_problem(const ScsData *d, const ScsCone *k, const ScsSettings *s, const char *filename);

@@ -23,6 +23,16 @@
 // of init.  The host equilibrates every problem and writes its values into the problem's own padded rows and dense P; H is then
 // per problem, and the problem's workgroup assembles, factors and inverts it in working precision before the first iteration
 // (sb_factor, k_small_batch<true, .>).  k_small_batch<false, .> is the shared kernel, unchanged.
+//
+// The host half (from struct ScsAmdSmall down) says each thing once.  small_kernel names the four instantiations, and the occupancy
+// query and the launch both take the kernel from it; small_grid_default is the default grid of either entry's kernel; small_ry is
+// the host's R_y of a row and small_equilibrate a problem's D, E (the identity with normalize = 0), for init and the set call alike;
+// the kernel's argument is filled once, by small_device_init, with what is the object's, and a launch sets what is the chunk's.
+// small_solve is a frame -- the listener, the try / catch, the chunk loop with SIGINT between launches, the counters -- around
+// small_solve_accepts (the checks, arguments before state), small_stage (one problem's scs_update and warm start), small_launch
+// and small_return (one problem's finalize).  (Un)normalisation with a problem's own sigma is normalize_sol_scaled /
+// un_normalize_sol_scaled of equilibrate.cpp, as in the family solve.  The SIGINT path and the catch path have no test: they were
+// kept by reading.
 #include <cstdarg>
 #include <memory>
 #include <type_traits>
@@ -467,8 +477,9 @@ struct ScsAmdSmall {
   bool cap_warm = false;
   DevBuf<real> dB, dC, dV, dS, dXYS, dQ;
   DevBuf<int> dIt;
-  std::vector<real> hB, hC, hV, hS, hXYS, hQ;
+  std::vector<real> hB, hC, hV, hS, hXYS, hQ, hWs; // hWs: the s of one problem's warm start (m)
   std::vector<int> hIt;
+  SbArgsOwn args{}; // what is the object's, filled once by small_device_init; a chunk copies it and sets what is its own
   int grid_user = 0, grid_default = 1, wg_per_cu = 0;
   int block = SB_BLOCK; // the instantiation, chosen once at init: SB_BLOCK (narrow) or SB_BLOCK_WIDE
   size_t lds_bytes = 0;
@@ -496,7 +507,8 @@ struct ScsAmdSmall {
 
 static thread_local std::string g_small_refusal;
 static thread_local bool g_small_refused = false;
-static void small_refuse(const char *fmt, ...) {
+// says why a call is not served; false, so that a check of the arguments reads `return small_refuse(...)`
+static bool small_refuse(const char *fmt, ...) {
   char buf[256];
   va_list ap;
   va_start(ap, fmt);
@@ -505,6 +517,7 @@ static void small_refuse(const char *fmt, ...) {
   g_small_refusal = buf;
   g_small_refused = true;
   printf("ERROR: scs_amd_small: %s\n", buf);
+  return false;
 }
 
 // H^-1 and the full symmetric P, dense n x n, from the equilibrated A (CSC) and P (upper triangle, CSC); false when H is not
@@ -592,17 +605,35 @@ static const void *small_kernel(const ScsAmdSmall *s, bool own) {
              : reinterpret_cast<const void *>(k_small_batch<false, SB_BLOCK_WIDE>);
 }
 
-// the dynamic LDS of the instantiation and what the CU then holds of it; 0 workgroups is an error, not a grid of one (the wide
-// kernel asks for nearly the whole CU: a build whose static LDS leaves less room must say so).  Throws HipError.
-static int small_wg_per_cu(const ScsAmdSmall *s, bool own) {
+// The default grid of an instantiation, what the chip holds of it at once: its dynamic LDS is set, and the workgroups a CU then
+// holds times the CUs.  0 workgroups is an error, not a grid of one (the wide kernel asks for nearly the whole CU: a build whose
+// static LDS leaves less room must say so).  Throws HipError.
+static int small_grid_default(ScsAmdSmall *s, bool own) {
   const void *kp = small_kernel(s, own);
   HIP_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes));
-  int per_cu = 0;
+  int per_cu = 0, cus = 0;
   HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, s->block, s->lds_bytes));
   if (per_cu < 1)
     throw HipError("scs_amd_small: no workgroup of " + std::to_string(s->block) + " threads with " + std::to_string(s->lds_bytes) +
                    " B of LDS fits a CU of this device");
-  return per_cu;
+  if (!own) s->wg_per_cu = per_cu; // scs_amd_small_get_occupancy reports the shared kernel
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+  return std::max(1, cus) * per_cu;
+}
+
+// the host's R_y of row i (the kernel's R lambda on rows n .. n + m): 1 / (1000 scale) on the zero cone, 1 / scale elsewhere
+static real small_ry(const ScsAmdSmall *s, int i) {
+  return i < s->k.z ? (real)1.0 / ((real)1000. * s->stgs.scale) : (real)1.0 / s->stgs.scale;
+}
+
+// D, E of one problem's matrices, which are equilibrated in place (the host passes of scs_init); normalize = 0: the identity
+static void small_equilibrate(const ScsAmdSmall *s, HostCsc *P, HostCsc &A, Scaling &sc) {
+  if (s->stgs.normalize) {
+    equilibrate(P, A, &s->k, sc);
+  } else {
+    sc.D.assign(s->m, (real)1);
+    sc.E.assign(s->n, (real)1);
+  }
 }
 
 static void small_ensure(ScsAmdSmall *s, size_t chunk, bool warm) {
@@ -621,6 +652,15 @@ static void small_ensure(ScsAmdSmall *s, size_t chunk, bool warm) {
     s->dV.alloc(s->cap * (size_t)s->l);
     s->cap_warm = true;
   }
+  const size_t n = s->n, m = s->m; // the host side of the staging: vectors keep their capacity
+  s->hB.resize(chunk * m);
+  s->hC.resize(chunk * n);
+  s->hS.resize(chunk * 3);
+  s->hXYS.resize(chunk * (n + 2 * m));
+  s->hQ.resize(chunk * SB_QS);
+  s->hIt.resize(chunk * 2);
+  s->hWs.resize(m);
+  if (warm) s->hV.resize(chunk * (size_t)s->l);
 }
 
 // the device side of an object, created by its first accepted solve (init is host work only: a refusal, and a machine without a
@@ -634,11 +674,7 @@ static void small_device_init(ScsAmdSmall *s) {
   HIP_CHECK(hipSetDevice(s->device));
   if (!s->stream) HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
-  auto up = [&](DevBuf<real> &b, const std::vector<real> &h) {
-    b.alloc(h.size());
-    b.upload(h.data(), h.size(), st);
-  };
-  auto upi = [&](DevBuf<int> &b, const std::vector<int> &h) {
+  auto up = [&](auto &b, const auto &h) {
     b.alloc(h.size());
     b.upload(h.data(), h.size(), st);
   };
@@ -648,17 +684,22 @@ static void small_device_init(ScsAmdSmall *s) {
   up(s->Pd, s->h_Pd);
   up(s->D, s->scal.D);
   up(s->E, s->scal.E);
-  upi(s->Ai, s->h_ai);
-  upi(s->Ati, s->h_ati);
-  upi(s->qoff, s->h_qoff);
-  upi(s->qlen, s->h_qlen);
+  up(s->Ai, s->h_ai);
+  up(s->Ati, s->h_ati);
+  up(s->qoff, s->h_qoff);
+  up(s->qlen, s->h_qlen);
   s->counter.alloc(1);
   HIP_CHECK(hipStreamSynchronize(st));
   s->lds_bytes = sb_lds_values(n, m, s->block) * sizeof(real);
-  int cus = 0;
-  s->wg_per_cu = small_wg_per_cu(s, false);
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-  s->grid_default = std::max(1, cus) * s->wg_per_cu; // what the chip holds at once
+  s->grid_default = small_grid_default(s, false);
+  SbArgsOwn &a = s->args; // the chunk's part (nprob, warm, the staging, the own-values blocks and the slab) is set by small_launch
+  a.n = n; a.m = m; a.l = s->l; a.z = (int)s->k.z; a.nl = (int)s->k.l; a.qsize = (int)s->k.qsize; a.has_P = s->has_P ? 1 : 0;
+  a.normalize = s->stgs.normalize ? 1 : 0; a.max_iters = (int)s->stgs.max_iters; a.wA = s->wA; a.wAt = s->wAt;
+  a.rho_x = s->stgs.rho_x; a.scale = s->stgs.scale; a.alpha = s->stgs.alpha; a.eps_abs = s->stgs.eps_abs; a.eps_rel = s->stgs.eps_rel;
+  a.eps_infeas = s->stgs.eps_infeas;
+  a.Av = s->Av.p; a.Atv = s->Atv.p; a.Hinv = s->Hinv.p; a.Pd = s->Pd.p; a.D = s->D.p; a.E = s->E.p;
+  a.Ai = s->Ai.p; a.Ati = s->Ati.p; a.qoff = s->qoff.p; a.qlen = s->qlen.p;
+  a.counter = s->counter.p;
   s->on_device = true;
   for (std::vector<real> *v : {&s->h_av, &s->h_atv, &s->h_Hinv, &s->h_Pd}) std::vector<real>().swap(*v);
   for (std::vector<int> *v : {&s->h_ai, &s->h_ati, &s->h_qoff, &s->h_qlen}) std::vector<int>().swap(*v);
@@ -729,15 +770,10 @@ ScsAmdSmall *scs_amd_small_init(const ScsData *d, const ScsCone *k, const ScsSet
   if (s->has_P) P.copy_from(d->P);
   s->patA = A; // the pattern scs_amd_small_set_values writes values on
   if (s->has_P) s->patP = P;
-  if (stgs->normalize) {
-    equilibrate(s->has_P ? &P : nullptr, A, &s->k, s->scal);
-  } else {
-    s->scal.D.assign(m, (real)1);
-    s->scal.E.assign(n, (real)1);
-  }
+  small_equilibrate(s.get(), s->has_P ? &P : nullptr, A, s->scal);
   std::vector<real> Ry(m), Hinv, Pd, av, atv;
   std::vector<int> ai, ati, qoff, qlen;
-  for (int i = 0; i < m; ++i) Ry[i] = i < k->z ? (real)1.0 / ((real)1000. * stgs->scale) : (real)1.0 / stgs->scale;
+  for (int i = 0; i < m; ++i) Ry[i] = small_ry(s.get(), i);
   if (!small_factor(A, s->has_P ? &P : nullptr, Ry, stgs->rho_x, Hinv, Pd)) {
     small_refuse("the reduced matrix R_x + P + A' R_y^-1 A is not positive definite (P must be positive semidefinite)");
     return nullptr;
@@ -785,49 +821,141 @@ void scs_amd_small_get_occupancy(const ScsAmdSmall *s, long long out[5]) {
   out[4] = s->block;
 }
 
-// scs_amd_small_solve (own = false) and scs_amd_small_solve_values (own = true: the values, D and E of the last set call)
+// ---- the steps of small_solve: the checks of a call, one problem's way in, a chunk's launch, one problem's way out ------------
+// false, with the refusal said, when the call is not served
+static bool small_solve_accepts(const ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
+                                const ScsSolution *sols, const ScsInfo *infos, bool own) {
+  if (!s || !B || !Cc || !sols || !infos) return small_refuse("missing ScsAmdSmall, B, Cc, ScsSolution or ScsInfo (a NULL argument)");
+  if (nprob < 1) return small_refuse("nprob < 1");
+  const int n = s->n, m = s->m;
+  if ((long long)ldb < m || (long long)ldc < n) return small_refuse("short leading dimension: ldb < m or ldc < n");
+  for (scs_int p = 0; p < nprob; ++p) {
+    if (!all_finite(B + (size_t)p * (size_t)ldb, (size_t)m) || !all_finite(Cc + (size_t)p * (size_t)ldc, (size_t)n))
+      return small_refuse("non-finite values in B or Cc (problem %lld)", (long long)p);
+    if (!sols[p].x || !sols[p].y || !sols[p].s) return small_refuse("sols[%lld].x, y or s is NULL (a NULL argument)", (long long)p);
+  }
+  // what depends on the object's state comes last: the checks of the arguments above need no accepted set call
+  if (own && s->vals_nprob == 0) return small_refuse("no values are set (scs_amd_small_set_values comes first)");
+  if (own && (long long)nprob != s->vals_nprob)
+    return small_refuse("nprob = %lld, but the values were set for %lld problems", (long long)nprob, s->vals_nprob);
+  return true;
+}
+
+// scs_update (:1287-1325) and, with warm, the warm start (:660-687) of the problem in slot p of the chunk's staging: the norms of
+// (b, c) as given, b and c normalised with the problem's own sigma, v = [x; y + s / R_y; 1] from the caller's normalised (x, y, s).
+// sc: the D, E the problem's matrices were equilibrated with -- the object's, or the problem's own; in small_return too.
+static void small_stage(ScsAmdSmall *s, int p, const Scaling &sc, const scs_float *bk, const scs_float *ck, const ScsSolution &sol, bool warm) {
+  const int n = s->n, m = s->m, l = s->l;
+  const bool norm = s->stgs.normalize != 0;
+  real *b = s->hB.data() + (size_t)p * m, *c = s->hC.data() + (size_t)p * n;
+  std::copy(bk, bk + m, b);
+  std::copy(ck, ck + n, c);
+  real nb = 0, nc = 0, sg = 1;
+  for (int i = 0; i < m; ++i) nb = std::max(nb, (real)std::fabs(b[i]));
+  for (int j = 0; j < n; ++j) nc = std::max(nc, (real)std::fabs(c[j]));
+  if (norm) sg = normalize_b_c_sigma(sc, b, c);
+  s->hS[3 * (size_t)p] = sg;
+  s->hS[3 * (size_t)p + 1] = nb;
+  s->hS[3 * (size_t)p + 2] = nc;
+  if (!warm) return;
+  real *v = s->hV.data() + (size_t)p * l, *x = v, *y = v + n, *sv = s->hWs.data();
+  std::copy(sol.x, sol.x + n, x);
+  std::copy(sol.y, sol.y + m, y);
+  std::copy(sol.s, sol.s + m, sv);
+  if (norm) normalize_sol_scaled(sc, sg, sg, x, y, sv);
+  for (int j = 0; j < n; ++j) x[j] = x[j] != x[j] ? (real)0 : x[j];
+  for (int i = 0; i < m; ++i) {
+    const real tt = y[i] + sv[i] / small_ry(s, i);
+    y[i] = tt != tt ? (real)0 : tt;
+  }
+  v[l - 1] = 1;
+}
+
+// The chunk of K staged problems, the first of them problem `done` of the call: the staging goes up, one launch of the object's
+// instantiation on min(K, the grid) workgroups, the results come down; returns with the stream idle.  Returns the grid.  Throws
+// HipError.
+static int small_launch(ScsAmdSmall *s, int K, size_t done, bool warm, bool own) {
+  const size_t n = s->n, m = s->m, l = s->l, ow = n + 2 * m;
+  hipStream_t st = s->stream;
+  s->dB.upload(s->hB.data(), (size_t)K * m, st);
+  s->dC.upload(s->hC.data(), (size_t)K * n, st);
+  s->dS.upload(s->hS.data(), (size_t)K * 3, st);
+  if (warm) s->dV.upload(s->hV.data(), (size_t)K * l, st);
+  HIP_CHECK(hipMemsetAsync(s->counter.p, 0, sizeof(int), st));
+  SbArgsOwn a = s->args;
+  a.nprob = K; a.warm = warm ? 1 : 0;
+  a.Bn = s->dB.p; a.Cn = s->dC.p; a.V0 = warm ? s->dV.p : nullptr; a.scal = s->dS.p;
+  a.xys = s->dXYS.p; a.q = s->dQ.p; a.it = s->dIt.p;
+  const int grid = std::min(K, s->grid_user > 0 ? s->grid_user : (own ? s->grid_default_own : s->grid_default));
+  if (own) {
+    a.Av = s->vAv.p + done * m * s->wA; a.Atv = s->vAtv.p + done * n * s->wAt; a.Hinv = nullptr;
+    a.Pd = s->has_P ? s->vPd.p + done * n * n : nullptr; a.D = s->vD.p + done * m; a.E = s->vE.p + done * n;
+    if ((size_t)grid > s->slab_grid) { // the slab follows the grid, not the number of problems
+      s->slab_grid = 0;
+      s->slab.alloc((size_t)grid * 2 * n * n);
+      s->slab_grid = (size_t)grid;
+    }
+    a.slab = s->slab.p;
+  }
+  // the shared kernel's parameter is an SbArgs: the base of the struct filled above
+  void *arg[] = {own ? static_cast<void *>(&a) : static_cast<void *>(static_cast<SbArgs *>(&a))};
+  (void)hipLaunchKernel(small_kernel(s, own), dim3(grid), dim3(s->block), arg, s->lds_bytes, st);
+  HIP_CHECK(hipGetLastError());
+  s->dXYS.download(s->hXYS.data(), (size_t)K * ow, st);
+  s->dQ.download(s->hQ.data(), (size_t)K * SB_QS, st);
+  s->dIt.download(s->hIt.data(), (size_t)K * 2, st);
+  HIP_CHECK(hipStreamSynchronize(st));
+  return grid;
+}
+
+// finalize (:825-969) of the problem in slot p of the chunk that came down: its (x, y, s) un-normalised into sol, its reduced
+// scalars into info; the failed pivot of the device factor fails this problem alone
+static void small_return(ScsAmdSmall *s, int p, const Scaling &sc, bool own, double chunk_ms, double t_call, ScsSolution *sol, ScsInfo *info) {
+  const int n = s->n, m = s->m;
+  const bool norm = s->stgs.normalize != 0;
+  if (own && s->hIt[2 * (size_t)p + 1] == SCS_FAILED) { // the device factor's pivot test: this problem alone
+    memset(info, 0, sizeof *info);
+    fail_out(nullptr, m, n, sol, info, SCS_FAILED, "the reduced matrix R_x + P + A' R_y^-1 A of this problem is not positive definite",
+             "failure");
+    return;
+  }
+  const real sg = s->hS[3 * (size_t)p];
+  const real *o = s->hXYS.data() + (size_t)p * ((size_t)n + 2 * (size_t)m);
+  std::copy(o, o + n, sol->x);
+  std::copy(o + n, o + n + m, sol->y);
+  std::copy(o + n + m, o + n + 2 * (size_t)m, sol->s);
+  if (norm) un_normalize_sol_scaled(sc, sg, sg, sol->x, sol->y, sol->s);
+  Resid r_n, r_o;
+  const int iter = s->hIt[2 * (size_t)p];
+  fill_residuals(r_n, r_o, s->hQ.data() + (size_t)p * SB_QS, 1, iter, s->has_P, norm, sg, sg);
+  memset(info, 0, sizeof *info);
+  strcpy(info->lin_sys_solver, "dense-direct-small-batch-hip-gfx950");
+  info->status_val = s->hIt[2 * (size_t)p + 1];
+  info->iter = iter;
+  info->setup_time = (real)s->setup_time;
+  info->scale = s->stgs.scale;
+  info->aa_stats.last_aa_norm = (real)NAN;
+  const LoopEnd e{(int)s->stgs.max_iters, 0, false};
+  finalize_status(r_o, n, m, e, sol, info);
+  info->solve_time = (real)chunk_ms; // the launch's wall time, the same in every problem of it
+  s->counters[3] += iter;
+  if (s->stgs.verbose) print_summary_row(r_o, iter, s->stgs.scale, (now_ms() - t_call + s->setup_time) / 1e3);
+}
+
+// scs_amd_small_solve (own = false) and scs_amd_small_solve_values (own = true: the values, D and E of the last set call): the
+// frame around the steps above -- the listener, the chunk loop with SIGINT looked at between launches, the counters, and the
+// failure of every problem on a HIP error
 static scs_int small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, scs_int ldb, const scs_float *Cc, scs_int ldc,
                            ScsSolution *sols, ScsInfo *infos, scs_int warm_start, bool own) {
   g_small_refused = false;
-  if (!s || !B || !Cc || !sols || !infos) {
-    small_refuse("missing ScsAmdSmall, B, Cc, ScsSolution or ScsInfo (a NULL argument)");
-    return SCS_FAILED;
-  }
-  if (nprob < 1) {
-    small_refuse("nprob < 1");
-    return SCS_FAILED;
-  }
-  const int n = s->n, m = s->m, l = s->l;
-  if ((long long)ldb < m || (long long)ldc < n) {
-    small_refuse("short leading dimension: ldb < m or ldc < n");
-    return SCS_FAILED;
-  }
-  for (scs_int p = 0; p < nprob; ++p) {
-    if (!all_finite(B + (size_t)p * (size_t)ldb, (size_t)m) || !all_finite(Cc + (size_t)p * (size_t)ldc, (size_t)n)) {
-      small_refuse("non-finite values in B or Cc (problem %lld)", (long long)p);
-      return SCS_FAILED;
-    }
-    if (!sols[p].x || !sols[p].y || !sols[p].s) {
-      small_refuse("sols[%lld].x, y or s is NULL (a NULL argument)", (long long)p);
-      return SCS_FAILED;
-    }
-  }
-  // what depends on the object's state comes last: the checks of the arguments above need no accepted set call
-  if (own && s->vals_nprob == 0) {
-    small_refuse("no values are set (scs_amd_small_set_values comes first)");
-    return SCS_FAILED;
-  }
-  if (own && (long long)nprob != s->vals_nprob) {
-    small_refuse("nprob = %lld, but the values were set for %lld problems", (long long)nprob, s->vals_nprob);
-    return SCS_FAILED;
-  }
+  if (!small_solve_accepts(s, nprob, B, ldb, Cc, ldc, sols, infos, own)) return SCS_FAILED;
+  const int n = s->n, m = s->m;
   InterruptListener listener;
   const double t_call = now_ms();
-  const bool warm = warm_start != 0, norm = s->stgs.normalize != 0;
+  const bool warm = warm_start != 0;
   try {
     small_device_init(s);
     HIP_CHECK(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
     bool sigint = false;
     for (scs_int done = 0; done < nprob; done += SB_CHUNK) {
       const int K = (int)std::min<scs_int>(SB_CHUNK, nprob - done);
@@ -838,116 +966,16 @@ static scs_int small_solve(ScsAmdSmall *s, scs_int nprob, const scs_float *B, sc
       }
       const double t0 = now_ms();
       small_ensure(s, (size_t)K, warm);
-      s->hB.resize((size_t)K * m);
-      s->hC.resize((size_t)K * n);
-      s->hS.resize((size_t)K * 3);
-      if (warm) s->hV.resize((size_t)K * l);
-      for (int p = 0; p < K; ++p) { // scs_update per problem (:1287-1325) and the warm start (:660-687)
-        const Scaling &sc = own ? s->vscal[(size_t)done + p] : s->scal;
-        real *b = s->hB.data() + (size_t)p * m, *c = s->hC.data() + (size_t)p * n;
-        std::copy(B + (size_t)(done + p) * (size_t)ldb, B + (size_t)(done + p) * (size_t)ldb + m, b);
-        std::copy(Cc + (size_t)(done + p) * (size_t)ldc, Cc + (size_t)(done + p) * (size_t)ldc + n, c);
-        real nb = 0, nc = 0, sg = 1;
-        for (int i = 0; i < m; ++i) nb = std::max(nb, (real)std::fabs(b[i]));
-        for (int j = 0; j < n; ++j) nc = std::max(nc, (real)std::fabs(c[j]));
-        if (norm) sg = normalize_b_c_sigma(sc, b, c);
-        s->hS[3 * (size_t)p] = sg;
-        s->hS[3 * (size_t)p + 1] = nb;
-        s->hS[3 * (size_t)p + 2] = nc;
-        if (warm) {
-          real *v = s->hV.data() + (size_t)p * l;
-          const ScsSolution &sol = sols[done + p];
-          for (int j = 0; j < n; ++j) {
-            const real x = norm ? sol.x[j] / (sc.E[j] / sg) : sol.x[j];
-            v[j] = x != x ? (real)0 : x;
-          }
-          for (int i = 0; i < m; ++i) {
-            const real y = norm ? sol.y[i] / (sc.D[i] / sg) : sol.y[i], sv = norm ? sol.s[i] * (sc.D[i] * sg) : sol.s[i];
-            const real ry = i < s->k.z ? (real)1.0 / ((real)1000. * s->stgs.scale) : (real)1.0 / s->stgs.scale;
-            const real tt = y + sv / ry;
-            v[n + i] = tt != tt ? (real)0 : tt;
-          }
-          v[l - 1] = 1;
-        }
-      }
-      s->dB.upload(s->hB.data(), (size_t)K * m, st);
-      s->dC.upload(s->hC.data(), (size_t)K * n, st);
-      s->dS.upload(s->hS.data(), (size_t)K * 3, st);
-      if (warm) s->dV.upload(s->hV.data(), (size_t)K * l, st);
-      HIP_CHECK(hipMemsetAsync(s->counter.p, 0, sizeof(int), st));
-      SbArgsOwn a;
-      a.n = n; a.m = m; a.l = l; a.z = (int)s->k.z; a.nl = (int)s->k.l; a.qsize = (int)s->k.qsize; a.has_P = s->has_P ? 1 : 0;
-      a.normalize = norm ? 1 : 0; a.max_iters = (int)s->stgs.max_iters; a.wA = s->wA; a.wAt = s->wAt; a.nprob = K; a.warm = warm ? 1 : 0;
-      a.rho_x = s->stgs.rho_x; a.scale = s->stgs.scale; a.alpha = s->stgs.alpha; a.eps_abs = s->stgs.eps_abs; a.eps_rel = s->stgs.eps_rel;
-      a.eps_infeas = s->stgs.eps_infeas;
-      a.Av = s->Av.p; a.Atv = s->Atv.p; a.Hinv = s->Hinv.p; a.Pd = s->Pd.p; a.D = s->D.p; a.E = s->E.p;
-      a.Ai = s->Ai.p; a.Ati = s->Ati.p; a.qoff = s->qoff.p; a.qlen = s->qlen.p;
-      a.Bn = s->dB.p; a.Cn = s->dC.p; a.V0 = warm ? s->dV.p : nullptr; a.scal = s->dS.p;
-      a.xys = s->dXYS.p; a.q = s->dQ.p; a.it = s->dIt.p; a.counter = s->counter.p;
-      const int grid = std::min(K, s->grid_user > 0 ? s->grid_user : (own ? s->grid_default_own : s->grid_default));
-      if (own) {
-        const size_t dn = (size_t)done;
-        a.Av = s->vAv.p + dn * m * s->wA; a.Atv = s->vAtv.p + dn * n * s->wAt; a.Hinv = nullptr;
-        a.Pd = s->has_P ? s->vPd.p + dn * n * n : nullptr; a.D = s->vD.p + dn * m; a.E = s->vE.p + dn * n;
-        if ((size_t)grid > s->slab_grid) { // the slab follows the grid, not the number of problems
-          s->slab_grid = 0;
-          s->slab.alloc((size_t)grid * 2 * n * n);
-          s->slab_grid = (size_t)grid;
-        }
-        a.slab = s->slab.p;
-        if (s->block == SB_BLOCK) hipLaunchKernelGGL((k_small_batch<true, SB_BLOCK>), dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, a);
-        else hipLaunchKernelGGL((k_small_batch<true, SB_BLOCK_WIDE>), dim3(grid), dim3(SB_BLOCK_WIDE), s->lds_bytes, st, a);
-      } else {
-        const SbArgs &as = a;
-        if (s->block == SB_BLOCK) hipLaunchKernelGGL((k_small_batch<false, SB_BLOCK>), dim3(grid), dim3(SB_BLOCK), s->lds_bytes, st, as);
-        else hipLaunchKernelGGL((k_small_batch<false, SB_BLOCK_WIDE>), dim3(grid), dim3(SB_BLOCK_WIDE), s->lds_bytes, st, as);
-      }
-      HIP_CHECK(hipGetLastError());
-      const size_t ow = (size_t)n + 2 * (size_t)m;
-      s->hXYS.resize((size_t)K * ow);
-      s->hQ.resize((size_t)K * SB_QS);
-      s->hIt.resize((size_t)K * 2);
-      s->dXYS.download(s->hXYS.data(), (size_t)K * ow, st);
-      s->dQ.download(s->hQ.data(), (size_t)K * SB_QS, st);
-      s->dIt.download(s->hIt.data(), (size_t)K * 2, st);
-      HIP_CHECK(hipStreamSynchronize(st));
+      // problem p of the chunk is problem done + p of the call: its column of B and Cc, its sols / infos and, own values, its D and E
+      auto scaling = [&](int p) -> const Scaling & { return own ? s->vscal[(size_t)done + p] : s->scal; };
+      for (int p = 0; p < K; ++p)
+        small_stage(s, p, scaling(p), B + (size_t)(done + p) * (size_t)ldb, Cc + (size_t)(done + p) * (size_t)ldc, sols[done + p], warm);
+      const int grid = small_launch(s, K, (size_t)done, warm, own);
       const double chunk_ms = now_ms() - t0;
       s->counters[0] += 1;
       s->counters[1] += grid;
       s->counters[2] += K;
-      for (int p = 0; p < K; ++p) { // finalize (:825-969) per problem
-        ScsSolution *sol = &sols[done + p];
-        ScsInfo *info = &infos[done + p];
-        if (own && s->hIt[2 * (size_t)p + 1] == SCS_FAILED) { // the device factor's pivot test: this problem alone
-          memset(info, 0, sizeof *info);
-          fail_out(nullptr, m, n, sol, info, SCS_FAILED, "the reduced matrix R_x + P + A' R_y^-1 A of this problem is not positive definite",
-                   "failure");
-          continue;
-        }
-        const Scaling &sc = own ? s->vscal[(size_t)done + p] : s->scal;
-        const real sg = s->hS[3 * (size_t)p];
-        const real *o = s->hXYS.data() + (size_t)p * ow;
-        for (int j = 0; j < n; ++j) sol->x[j] = norm ? o[j] * (sc.E[j] / sg) : o[j];
-        for (int i = 0; i < m; ++i) {
-          sol->y[i] = norm ? o[n + i] * (sc.D[i] / sg) : o[n + i];
-          sol->s[i] = norm ? o[n + m + i] / (sc.D[i] * sg) : o[n + m + i];
-        }
-        Resid r_n, r_o;
-        const int iter = s->hIt[2 * (size_t)p];
-        fill_residuals(r_n, r_o, s->hQ.data() + (size_t)p * SB_QS, 1, iter, s->has_P, norm, sg, sg);
-        memset(info, 0, sizeof *info);
-        strcpy(info->lin_sys_solver, "dense-direct-small-batch-hip-gfx950");
-        info->status_val = s->hIt[2 * (size_t)p + 1];
-        info->iter = iter;
-        info->setup_time = (real)s->setup_time;
-        info->scale = s->stgs.scale;
-        info->aa_stats.last_aa_norm = (real)NAN;
-        const LoopEnd e{(int)s->stgs.max_iters, 0, false};
-        finalize_status(r_o, n, m, e, sol, info);
-        info->solve_time = (real)chunk_ms; // the launch's wall time, the same in every problem of it
-        s->counters[3] += iter;
-        if (s->stgs.verbose) print_summary_row(r_o, iter, s->stgs.scale, (now_ms() - t_call + s->setup_time) / 1e3);
-      }
+      for (int p = 0; p < K; ++p) small_return(s, p, scaling(p), own, chunk_ms, t_call, &sols[done + p], &infos[done + p]);
     }
   } catch (const std::exception &ex) {
     fprintf(stderr, "%s\n", ex.what());
@@ -978,46 +1006,32 @@ void scs_amd_small_free_values(ScsAmdSmall *s) {
   s->vals_nprob = 0;
 }
 
+// the checks of scs_amd_small_set_values: false, with the refusal said, when the call is not served
+static bool small_set_accepts(const ScsAmdSmall *s, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
+  if (!s || !AX) return small_refuse("missing ScsAmdSmall or AX (a NULL argument)");
+  if (PX && !s->has_P) return small_refuse("PX given, but the object was built without a P");
+  if (!PX && s->has_P) return small_refuse("PX missing (a NULL argument): the object was built with a P");
+  if (nprob < 1) return small_refuse("nprob < 1");
+  const size_t nzA = (size_t)s->patA.p[s->n], nzP = s->has_P ? (size_t)s->patP.p[s->n] : 0;
+  if ((long long)ldax < (long long)nzA || (s->has_P && (long long)ldpx < (long long)nzP))
+    return small_refuse("short leading dimension: ldax < nnz(A) = %lld or ldpx < nnz(P) = %lld", (long long)nzA, (long long)nzP);
+  for (scs_int p = 0; p < nprob; ++p)
+    if ((nzA && !all_finite(AX + (size_t)p * (size_t)ldax, nzA)) || (nzP && !all_finite(PX + (size_t)p * (size_t)ldpx, nzP)))
+      return small_refuse("non-finite values in AX or PX (problem %lld)", (long long)p);
+  return true;
+}
+
 scs_int scs_amd_small_set_values(ScsAmdSmall *s, scs_int nprob, const scs_float *AX, scs_int ldax, const scs_float *PX, scs_int ldpx) {
   g_small_refused = false;
-  if (!s || !AX) {
-    small_refuse("missing ScsAmdSmall or AX (a NULL argument)");
-    return SCS_FAILED;
-  }
-  if (PX && !s->has_P) {
-    small_refuse("PX given, but the object was built without a P");
-    return SCS_FAILED;
-  }
-  if (!PX && s->has_P) {
-    small_refuse("PX missing (a NULL argument): the object was built with a P");
-    return SCS_FAILED;
-  }
-  if (nprob < 1) {
-    small_refuse("nprob < 1");
-    return SCS_FAILED;
-  }
+  if (!small_set_accepts(s, nprob, AX, ldax, PX, ldpx)) return SCS_FAILED;
   const int n = s->n, m = s->m;
   const size_t nzA = (size_t)s->patA.p[n], nzP = s->has_P ? (size_t)s->patP.p[n] : 0;
-  if ((long long)ldax < (long long)nzA || (s->has_P && (long long)ldpx < (long long)nzP)) {
-    small_refuse("short leading dimension: ldax < nnz(A) = %lld or ldpx < nnz(P) = %lld", (long long)nzA, (long long)nzP);
-    return SCS_FAILED;
-  }
-  for (scs_int p = 0; p < nprob; ++p)
-    if ((nzA && !all_finite(AX + (size_t)p * (size_t)ldax, nzA)) || (nzP && !all_finite(PX + (size_t)p * (size_t)ldpx, nzP))) {
-      small_refuse("non-finite values in AX or PX (problem %lld)", (long long)p);
-      return SCS_FAILED;
-    }
   scs_amd_small_free_values(s); // a second set call replaces the values; a failure below leaves none
   try {
     small_device_init(s);
     HIP_CHECK(hipSetDevice(s->device));
     hipStream_t st = s->stream;
-    if (s->grid_default_own == 0) {
-      int cus = 0;
-      const int per_cu = small_wg_per_cu(s, true);
-      HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-      s->grid_default_own = std::max(1, cus) * per_cu;
-    }
+    if (s->grid_default_own == 0) s->grid_default_own = small_grid_default(s, true); // the own-values kernel, set up by the first set call
     const size_t wA = s->wA, wAt = s->wAt, szA = (size_t)m * wA, szAt = (size_t)n * wAt, szP = s->has_P ? (size_t)n * n : 0;
     if (s->mapA.size() != nzA || s->mapAt.size() != nzA) { // the slots small_ell gives the entries, in its order
       s->mapA.resize(nzA);
@@ -1052,12 +1066,7 @@ scs_int scs_amd_small_set_values(ScsAmdSmall *s, scs_int nprob, const scs_float 
         Scaling &sc = s->vscal[p];
         std::copy(AX + p * (size_t)ldax, AX + p * (size_t)ldax + nzA, A.x.begin());
         if (s->has_P) std::copy(PX + p * (size_t)ldpx, PX + p * (size_t)ldpx + nzP, P.x.begin());
-        if (s->stgs.normalize) {
-          equilibrate(s->has_P ? &P : nullptr, A, &s->k, sc);
-        } else {
-          sc.D.assign(m, (real)1);
-          sc.E.assign(n, (real)1);
-        }
+        small_equilibrate(s, s->has_P ? &P : nullptr, A, sc);
         real *av = hAv.data() + q * szA, *atv = hAtv.data() + q * szAt, *pd = hPd.data() + q * szP;
         for (size_t e = 0; e < nzA; ++e) {
           av[s->mapA[e]] = A.x[e];

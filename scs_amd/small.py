@@ -19,8 +19,6 @@ import numpy as np
 
 from . import capi
 
-_IGNORED = {"use_indirect", "gpu", "mkl", "linear_solver"}
-
 
 def limits(lib=None):
     """(largest n, largest n + m + 1) the library serves"""
@@ -38,26 +36,18 @@ class SmallBatch:
         self._nvalues = 0  # problems of the last set_values
         if any(k not in data for k in ("A", "b", "c")):
             raise ValueError("data must contain 'A', 'b' and 'c'")
-        cone = dict(cone)
-        if "f" in cone:
-            cone["z"] = cone.pop("f") + cone.get("z", 0)
-        for k in ("q", "s", "cs", "p", "bu", "bl"):
-            if k in cone and np.isscalar(cone[k]):
-                cone[k] = [cone[k]]
+        cone, kw = capi.cone_and_settings(cone, settings, adaptive_scale=0, acceleration_lookback=0)
         self._prob = capi.Problem(data["A"], data["b"], data["c"], cone, P=data.get("P"), T=self._T)
-        kw = {k: v for k, v in settings.items() if k not in _IGNORED}
-        for k in ("write_data_filename", "log_csv_filename"):
-            if isinstance(kw.get(k), str):
-                kw[k] = kw[k].encode()
-        kw.setdefault("verbose", 0)
-        kw.setdefault("adaptive_scale", 0)
-        kw.setdefault("acceleration_lookback", 0)
         self._settings = capi.default_settings(self._lib, **kw)
         self.limits = limits(self._lib)
         self._h = self._lib.scs_amd_small_init(ct.byref(self._prob.data), ct.byref(self._prob.k), ct.byref(self._settings))
         if not self._h:
-            why = self._lib.scs_amd_small_refusal()
-            raise ValueError("scs_amd_small_init: " + (why.decode() if why else "failed (no HIP device, or a HIP error: see stderr)"))
+            self._fail("scs_amd_small_init", ValueError("scs_amd_small_init: failed (no HIP device, or a HIP error: see stderr)"))
+
+    def _fail(self, entry, otherwise):
+        """a call of `entry` that did not return 0: ValueError with the library's message where it refused, else `otherwise`"""
+        why = self._lib.scs_amd_small_refusal()
+        raise ValueError(f"{entry}: {why.decode()}") if why else otherwise
 
     @property
     def n(self):
@@ -106,10 +96,7 @@ class SmallBatch:
                                                 max(1, PX.shape[0]) if PX is not None else 0)
         if rc != 0:
             self._nvalues = 0
-            why = self._lib.scs_amd_small_refusal()
-            if why:
-                raise ValueError("scs_amd_small_set_values: " + why.decode())
-            raise RuntimeError("scs_amd_small_set_values failed on the device (see stderr)")
+            self._fail("scs_amd_small_set_values", RuntimeError("scs_amd_small_set_values failed on the device (see stderr)"))
         self._nvalues = K
 
     def free_values(self):
@@ -143,39 +130,30 @@ class SmallBatch:
             raise ValueError("B and C must be finite")
         B, Cc = np.asfortranarray(B), np.asfortranarray(Cc)
         K = B.shape[1]
-        X, Y, S = (np.zeros((n, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"), np.zeros((m, K), dtype=f, order="F"))
         if warm is not None:
             if len(warm) != 3:
                 raise ValueError("warm must be (X, Y, S)")
-            for dst, src, nm in ((X, warm[0], "X"), (Y, warm[1], "Y"), (S, warm[2], "S")):
+            blocks = []
+            for src, nm, rows in zip(warm, "XYS", (n, m, m)):
                 src = np.asarray(src, dtype=f)
-                if src.ndim == 1:
-                    src = src[:, None]
-                if src.shape != dst.shape:
-                    raise ValueError(f"warm {nm} must have shape {dst.shape}")
-                dst[:] = src
-        sols = (T.ScsSolution * K)()
-        infos = (T.ScsInfo * K)()
-        sz = np.dtype(f).itemsize
-        for k in range(K):
-            sols[k].x = ct.cast(X.ctypes.data + k * n * sz, T.fp)
-            sols[k].y = ct.cast(Y.ctypes.data + k * m * sz, T.fp)
-            sols[k].s = ct.cast(S.ctypes.data + k * m * sz, T.fp)
+                src = src[:, None] if src.ndim == 1 else src
+                if src.shape != (rows, K):
+                    raise ValueError(f"warm {nm} must have shape {(rows, K)}")
+                blocks.append(src)
+            warm = blocks
+        blk = capi.SolutionBlock(T, n, m, K, warm)
         if A is not None:  # after B, C and warm have passed: a refused call leaves the values of an earlier set_values in place
             self.set_values(A, P)
             own_values = True
         if own_values and self._nvalues and K != self._nvalues:
             raise ValueError(f"B and C hold {K} problems, but the values were set for {self._nvalues}")
         entry = self._lib.scs_amd_small_solve_values if own_values else self._lib.scs_amd_small_solve
-        rc = entry(self._h, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, sols, infos,
+        rc = entry(self._h, K, B.ctypes.data_as(T.fp), m, Cc.ctypes.data_as(T.fp), n, blk.sols, blk.infos,
                    1 if warm is not None else 0)
         if rc != 0:
             name = "scs_amd_small_solve_values" if own_values else "scs_amd_small_solve"
-            why = self._lib.scs_amd_small_refusal()
-            if why:
-                raise ValueError(f"{name}: " + why.decode())
-            raise RuntimeError(f"{name} failed on the device (see stderr)")
-        return [dict(x=X[:, k].copy(), y=Y[:, k].copy(), s=S[:, k].copy(), info=capi.info_dict(infos[k])) for k in range(K)]
+            self._fail(name, RuntimeError(f"{name} failed on the device (see stderr)"))
+        return blk.results()
 
     def set_grid(self, workgroups):
         """the number of workgroups of the following launches; 0: the default (what the chip holds at once)"""

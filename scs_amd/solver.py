@@ -21,8 +21,6 @@ import numpy as np
 
 from . import capi
 
-_IGNORED = {"use_indirect", "gpu", "mkl", "linear_solver"}
-
 
 class SCS:
     def __init__(self, data, cone, dtype="f64", **settings):
@@ -31,18 +29,8 @@ class SCS:
         self._w = None
         if any(k not in data for k in ("A", "b", "c")):
             raise ValueError("data must contain 'A', 'b' and 'c'")
-        cone = dict(cone)
-        if "f" in cone:  # scs < 3 name of the zero cone
-            cone["z"] = cone.pop("f") + cone.get("z", 0)
-        for k in ("q", "s", "cs", "p", "bu", "bl"):  # scs-python accepts scalars for single cones
-            if k in cone and np.isscalar(cone[k]):
-                cone[k] = [cone[k]]
+        cone, kw = capi.cone_and_settings(cone, settings)
         self._prob = capi.Problem(data["A"], data["b"], data["c"], cone, P=data.get("P"), T=self._T)
-        kw = {k: v for k, v in settings.items() if k not in _IGNORED}
-        for k in ("write_data_filename", "log_csv_filename"):
-            if isinstance(kw.get(k), str):
-                kw[k] = kw[k].encode()
-        kw.setdefault("verbose", 0)
         self._settings = capi.default_settings(self._lib, **kw)
         self._w = self._lib.scs_init(C.byref(self._prob.data), C.byref(self._prob.k), C.byref(self._settings))
         if not self._w:
